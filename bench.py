@@ -24,7 +24,18 @@ N > 1  : one process per GPU.  The headline is WEAK-scaled (the tier's rule
          a child job of the ranks (run_isolated), so a fault there cannot lose
          the line.
 
-Extra objects on the JSON line:
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K
+steps, writes its outputs when --dump-outputs DIR is given and prints the line.
+Everything else — the CPU baselines, the isolated per-launch median, the
+extras (other dtypes, sizes and tables, the provider's collectives, the N > 1
+strong-scaled form) — runs only with --full.
+
+--dump-outputs DIR writes DIR/dst.npy (DIR/dst_rank<r>.npy at N > 1): float32,
+sample_index()'s fixed sample of the dst buffer the last timed step wrote,
+4 Mi elements (16 MiB) over all ranks, so 4 Mi / N per rank.  The buffers are seeded and put back to their seeded contents
+after the clock prewarm, so equal arguments give equal files.
+
+Extra objects on the JSON line (cpu_baseline and extras with --full only):
   roofline      dominant kernel (combine_lds<SUM,float>): algorithmic bytes per
                 launch (3·S) ÷ its average duration from HIP events on the
                 launch stream; peak 8.0 TB/s (MI355X HBM3E spec); ``traffic``
@@ -35,7 +46,8 @@ Extra objects on the JSON line:
                 4 KiB allreduce through the provider's host path) and
                 configs[4]'s per-bucket double PROD combine.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+       python bench.py --full [--gpus N] [--steps K] [--warmup W] [--no-cpu]
        python bench.py --tune      # kernel-variant sweep (dev tool)
 """
 from __future__ import annotations
@@ -269,6 +281,18 @@ def make_buffers(dev, seed: int, count: int = COUNT, nsets: int | None = None):
         dst = torch.rand(count, device=dev, generator=g) * 2 - 1
         sets.append((dst, src))
     return sets
+
+
+def reseed_dst(sets, dev, seed: int, count: int) -> None:
+    """Put every dst of make_buffers(dev, seed, count, len(sets)) back to its
+    seeded contents: the same generator walked again (src's draw, then
+    dst's) through one scratch buffer."""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    tmp = torch.empty(count, device=dev)
+    for dst, _ in sets:
+        torch.rand(count, device=dev, generator=g, out=tmp)      # src's draw
+        torch.rand(count, device=dev, generator=g, out=tmp)
+        dst.copy_(tmp.mul_(2).sub_(1))
 
 
 def prewarm(step, min_s: float) -> int:
@@ -1972,7 +1996,15 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=100)
-    ap.add_argument("--no-cpu", action="store_true", help="skip cpu_baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the CPU baselines, the isolated per-launch "
+                         "kernel median and every extra (other dtypes, sizes, tables, "
+                         "provider collectives, N > 1 strong scaling); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step returned (this rank's dst) as "
+                         "DIR/<name>.npy, float32; a fixed seeded sample of the 256 MiB buffer, "
+                         "16 MiB over all ranks")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip cpu_baseline")
     ap.add_argument("--cpu-reps", type=int, default=5)
     ap.add_argument("--tune", action="store_true")
     ap.add_argument("--tune-rounds", type=int, default=10)
@@ -2001,6 +2033,8 @@ def main() -> None:
     ap.add_argument("--prewarm-s", type=float, default=0.25,
                     help="untimed clock-ramp launches before the W warmup steps (s)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.tune:
         tune(args)
@@ -2088,8 +2122,12 @@ def main() -> None:
     # Headline: every rank its own 256 MiB buffer pair per step (weak: the
     # combine partitions with no exchange, so N GPUs do N independent units).
     cnt = COUNT
-    r = timed_combine(dev, stream, cnt, 1000 + rank, args, world)
+    r = timed_combine(dev, stream, cnt, 1000 + rank, args, world,
+                      sample=dump_elems(world) if args.dump_outputs else 0,
+                      isolated=args.full)
     elapsed, kern_ms, kern_med = r["elapsed"], r["kern_ms"], r["kern_med"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"dst" if world == 1 else f"dst_rank{rank}": r["last_out"]})
     shard_bytes = cnt * 4
     value = 3 * S_BYTES * world * args.steps / elapsed / 2**30
     achieved = 3 * shard_bytes / (kern_ms * 1e-3) / 1e9
@@ -2131,11 +2169,10 @@ def main() -> None:
             "kernel": "combine_lds<FI_SUM,float,U=4> (LDS-DMA staged; nt stores at "
                       ">= 192 MiB per operand, sc1 write-through below)",
             "kernel_us": round(kern_ms * 1e3, 2),
-            "kernel_us_isolated_median": round(kern_med * 1e3, 2),
             "timing": "HIP event pair around the timed region on the launch stream, "
                       "divided by steps (includes inter-kernel dispatch gaps), max over "
-                      "ranks; isolated per-launch event median beside it; rocprofv3 "
-                      "kernel-trace summary in profiles/",
+                      "ranks; with --full the isolated per-launch event median beside it; "
+                      "rocprofv3 kernel-trace summary in profiles/",
             "algorithmic_bytes_per_launch": 3 * shard_bytes,
             "traffic_source": traffic_src,
             # HBM's own rate for this 2-read/1-write mix, measured apart
@@ -2149,7 +2186,9 @@ def main() -> None:
     }
     if REHEARSE:
         line["rehearsal"] = "LFA_BENCH_REHEARSE: ranks share GPUs; not a measurement"
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if kern_med is not None:
+        line["roofline"]["kernel_us_isolated_median"] = round(kern_med * 1e3, 2)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         line["cpu_baseline"] = cpu_baseline(args.cpu_reps)
         line["cpu_baseline"]["config3_int64_64mib"] = cpu_baseline_config3(args.cpu_reps)
         line["cpu_baseline"]["config1_2rank_4kib_allreduce_host"] = cpu_config1_peer()
@@ -2169,7 +2208,7 @@ def main() -> None:
         _emit("extras timed out")
         os._exit(0)
 
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         torch.cuda.empty_cache()
         t_extras = time.time()
         wd = threading.Timer(args.extras_timeout, _overrun)
@@ -2267,21 +2306,62 @@ def strong_scaling(line, dev, stream, args, world, rank) -> None:
     torch.cuda.empty_cache()
 
 
-def timed_combine(dev, stream, count: int, seed: int, args, world: int) -> dict:
+DUMP_SAMPLE = 1 << 22                  # elements --dump-outputs writes over ALL ranks (16 MiB)
+
+
+def dump_elems(world: int) -> int:
+    """One rank's share of the dump: the ranks' files together stay at
+    DUMP_SAMPLE elements (16 MiB of float32) whatever the world size."""
+    return DUMP_SAMPLE // max(1, world)
+
+
+def sample_index(count: int, n: int = DUMP_SAMPLE):
+    """The fixed `n`-element sample of a `count`-element output that
+    --dump-outputs writes: the first and the last n/8 elements, 64 Ki at the
+    most (the kernel's head and tail paths), and seeded draws from the whole
+    range, ascending; everything when the output is no larger than `n`."""
+    import numpy as np
+    if count <= n:
+        return np.arange(count, dtype=np.int64)
+    edge = min(1 << 16, n // 8)
+    draws = np.random.default_rng(0xD0).integers(0, count, n - 2 * edge, dtype=np.int64)
+    return np.sort(np.concatenate([np.arange(edge, dtype=np.int64), draws,
+                                   np.arange(count - edge, count, dtype=np.int64)]))
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def timed_combine(dev, stream, count: int, seed: int, args, world: int,
+                  sample: int = 0, isolated: bool = True, nsets: int | None = None) -> dict:
     """The bench step on this rank: float FI_SUM combine of `count` elements,
     rotating over enough buffer pairs to defeat the MALL.  W warmup launches
     (after a short time-based clock prewarm), then EXACTLY K timed launches
     between a barrier + synchronize on both sides; wall time and the launch
-    stream's event time are maxed over ranks."""
+    stream's event time are maxed over ranks.
+
+    The prewarm's launch count depends on the clock, and every launch adds
+    src into dst, so the dst buffers are put back to their seeded contents
+    after it: the W + K launches that follow start from the same data in
+    every run, and `sample` > 0 returns that many elements (sample_index) of
+    the dst the last timed launch wrote, taken before anything else runs
+    (last_out).  `nsets` overrides the number of rotated pairs (tests)."""
     from libfabric_amd import atomic
-    sets = make_buffers(dev, seed, count)
+    sets = make_buffers(dev, seed, count, nsets)
     nsets = len(sets)
 
     def step(i):
         d, s = sets[i % nsets]
         atomic.write(FI_SUM, FI_FLOAT, d, s, count, stream)
 
-    npre = prewarm(step, args.prewarm_s) if args.prewarm_s > 0 else 0
+    npre = 0
+    if args.prewarm_s > 0:
+        npre = prewarm(step, args.prewarm_s)
+        reseed_dst(sets, dev, seed, count)
     for i in range(args.warmup):
         step(i)
     torch.cuda.synchronize()
@@ -2302,18 +2382,25 @@ def timed_combine(dev, stream, count: int, seed: int, args, world: int) -> dict:
     # roofline: average launch duration = region GPU time / K (keeps the
     # ~1 us dispatch gap between consecutive kernels in: conservative).
     kern_ms = max_over_ranks(ev0.elapsed_time(ev1) / args.steps, world)
-    # Diagnostic only (not timed): per-launch event pairs, median.
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-           for _ in range(min(args.steps, 30))]
-    for i, (a, b) in enumerate(evs):
-        a.record(stream)
-        step(i)
-        b.record(stream)
-    torch.cuda.synchronize()
-    durs = [a.elapsed_time(b) for a, b in evs][3:] or [kern_ms]
+    last_out = None
+    if sample > 0:
+        idx = torch.from_numpy(sample_index(count, sample)).to(dev)
+        last_out = sets[(args.steps - 1) % nsets][0][idx].cpu().numpy()
+    kern_med = None
+    if isolated:
+        # Diagnostic only (not timed): per-launch event pairs, median.
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+               for _ in range(min(args.steps, 30))]
+        for i, (a, b) in enumerate(evs):
+            a.record(stream)
+            step(i)
+            b.record(stream)
+        torch.cuda.synchronize()
+        durs = [a.elapsed_time(b) for a, b in evs][3:] or [kern_ms]
+        kern_med = statistics.median(durs)
     del sets
-    return {"elapsed": elapsed, "kern_ms": kern_ms, "kern_med": statistics.median(durs),
-            "nsets": nsets, "prewarm": npre}
+    return {"elapsed": elapsed, "kern_ms": kern_ms, "kern_med": kern_med,
+            "nsets": nsets, "prewarm": npre, "last_out": last_out}
 
 
 if __name__ == "__main__":

@@ -94,6 +94,31 @@ def test_rotation_defeats_mall():
         assert bench.n_sets(ln) * 2 * ln * 4 >= (1 << 30)
 
 
+def test_dump_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: the same ascending sample in every run, head and tail
+    of the buffer included, float32 .npy files well under 64 MB; a small
+    output is written whole."""
+    import numpy as np
+    a, b = bench.sample_index(bench.COUNT), bench.sample_index(bench.COUNT)
+    assert np.array_equal(a, b) and a.dtype == np.int64
+    assert a.size == bench.DUMP_SAMPLE and a.size * 4 <= 64 * 1000 * 1000
+    assert a[0] == 0 and a[-1] == bench.COUNT - 1 and np.all(np.diff(a) >= 0)
+    assert np.isin(np.arange(1 << 16), a[:1 << 17]).all()
+    assert np.isin(np.arange(bench.COUNT - (1 << 16), bench.COUNT), a[-(1 << 17):]).all()
+    assert np.array_equal(bench.sample_index(1000), np.arange(1000))
+    # every rank writes its own file: the files of a job together stay at
+    # the one-rank size, far below 64 MB, for every world size the bench runs
+    for world in range(1, 9):
+        per = bench.sample_index(bench.COUNT, bench.dump_elems(world))
+        assert per.size == bench.dump_elems(world) and per[0] == 0 and per[-1] == bench.COUNT - 1
+        assert world * (per.size * 4 + 128) <= bench.DUMP_SAMPLE * 4 + 8 * 128 < 64 * 1000 * 1000
+    assert bench.sample_index(100, 16).size == 16
+    x = np.arange(6, dtype=np.float64) / 3
+    bench.dump_outputs(str(tmp_path / "o"), {"dst": x})
+    y = np.load(tmp_path / "o" / "dst.npy")
+    assert y.dtype == np.float32 and np.array_equal(y, x.astype(np.float32))
+
+
 def test_config3_data_distribution():
     import numpy as np
     x = bench.config3_data(3, 1 << 16)

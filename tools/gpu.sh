@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU stages for one gpurun call:   tools/gpu.sh <stage> [<stage> ...]
 # Each stage is one or more tools/gpu_step.sh steps (own time limit, log in
-# gpurun_out/<name>.log); stages run in order and the call stops at the first
+# $OUT/<name>.log); stages run in order and the call stops at the first
 # fault (gpu_step.sh exits 99 on anything but pass / ordinary test failure).
 #
 #   smoke        __graft_entry__.smoke()
@@ -9,8 +9,8 @@
 #   tests:<k>    pytest -m gpu -k <k>
 #   peer8        the 8-process executor test once at the default 4 hardware
 #                queues per process, per-rank LFA_TRACE / LFA_DEBUG logs under
-#                gpurun_out/peer_logs, HIP runtime errors (AMD_LOG_LEVEL=1)
-#   bench        driver-shaped bench (--gpus 1 --steps 20 --warmup 5) under
+#                $OUT/peer_logs, HIP runtime errors (AMD_LOG_LEVEL=1)
+#   bench        the full bench (--full --gpus 1 --steps 20 --warmup 5) under
 #                rocprofv3 --kernel-trace --stats
 #   benchplain   the same without the profiler
 #   pmc          the headline kernel's FETCH_SIZE / WRITE_SIZE in separate passes
@@ -37,7 +37,10 @@
 #   tablepmc     fetch / compare tables and 32 MiB buckets: kernel trace + PMC
 cd "$(dirname "$0")/.." || exit 1
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+# every stage writes its logs and profiler output under $OUT
+export LFA_GPU_OUT="${LFA_GPU_OUT:-gpu_out}"
+OUT=$LFA_GPU_OUT
+mkdir -p "$OUT"
 S=tools/gpu_step.sh
 P="rocprofv3 --kernel-trace --stats --output-format csv"
 PT="python3 -u -m pytest -x -v --timeout 200 --timeout-method thread"
@@ -51,17 +54,17 @@ for stage in "$@"; do
       k="${stage#tests:}"
       $S "tests_$(echo "$k" | tr -c 'A-Za-z0-9_\n' '_')" 600 $PT -m gpu tests -k "$k" || exit 99 ;;
     peer8)
-      mkdir -p gpurun_out/peer_logs
-      PEER_LOG_DIR=gpurun_out/peer_logs LFA_TRACE=1 AMD_LOG_LEVEL=1 LFA_TEST_HW_QUEUES=4 \
+      mkdir -p $OUT/peer_logs
+      PEER_LOG_DIR=$OUT/peer_logs LFA_TRACE=1 AMD_LOG_LEVEL=1 LFA_TEST_HW_QUEUES=4 \
         $S peer8 300 $PT -m gpu tests/test_coll_peer_gpu.py \
         -k "test_c_executor_gpu_kernels_across_processes and 8" || exit 99 ;;
     bench)
-      $S prof_bench 500 $P -d gpurun_out/prof_bench -o run -- python3 bench.py --gpus 1 --steps 20 --warmup 5 || exit 99 ;;
+      $S prof_bench 500 $P -d "$OUT/prof_bench" -o run -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 || exit 99 ;;
     benchplain)
-      $S bench 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 || exit 99 ;;
+      $S bench 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 || exit 99 ;;
     pmc)
-      $S pmc_fetch 150 timeout -s KILL 140 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -o run -- python3 bench.py --steps 20 --warmup 5 --no-cpu --no-extras && \
-      $S pmc_write 150 timeout -s KILL 140 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -o run -- python3 bench.py --steps 20 --warmup 5 --no-cpu --no-extras || exit 99 ;;
+      $S pmc_fetch 150 timeout -s KILL 140 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o run -- python3 bench.py --steps 20 --warmup 5 --no-cpu --no-extras && \
+      $S pmc_write 150 timeout -s KILL 140 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o run -- python3 bench.py --steps 20 --warmup 5 --no-cpu --no-extras || exit 99 ;;
     treeput)
       for lay in sep skew; do
         $S "tune_treeput_$lay" 400 python3 -u bench.py --tune-treeput --treeput-layout $lay \
@@ -76,7 +79,7 @@ for stage in "$@"; do
                "TA_BUSY_avr GRBM_GUI_ACTIVE" "WRITE_SIZE" "FETCH_SIZE"; do
         tag=$(echo "$c" | cut -d' ' -f1 | tr 'A-Z' 'a-z')
         $S "treeput_pmc_$tag" 150 timeout -s KILL 140 rocprofv3 --pmc $c --output-format csv \
-          -d "gpurun_out/treeput_pmc_$tag" -o run -- python3 bench.py --tune-treeput \
+          -d "$OUT/treeput_pmc_$tag" -o run -- python3 bench.py --tune-treeput \
           --variants "${TREEPUT_PMC_VARIANT:-0}" --tune-rounds 2 || exit 99
       done ;;
     clat)
@@ -93,7 +96,7 @@ for stage in "$@"; do
       LFA_DIRECT_FENCE=an LFA_DIRECT_PRELOAD=1 $S solo_fence_an_pl 200 \
         python3 -u tools/probe_solo_latency.py || exit 99 ;;
     sizes)
-      $S ksizes 300 $P -d gpurun_out/ksizes -o run -- python3 bench.py --only-extra sizes || exit 99 ;;
+      $S ksizes 300 $P -d $OUT/ksizes -o run -- python3 bench.py --only-extra sizes || exit 99 ;;
     host2)
       $S host2 300 python3 -u tools/probe_host_group_chunk.py || exit 99 ;;
     ipc)
@@ -133,16 +136,16 @@ for stage in "$@"; do
     rehearse2)
       # the N > 1 flow at 2 ranks sharing this GPU (LFA_BENCH_REHEARSE): the
       # provider rows through a peer-transfer domain, with their oracle checks
-      LFA_BENCH_REHEARSE=1 $S rehearse2 600 python3 -u bench.py --gpus 2 --steps 5 \
+      LFA_BENCH_REHEARSE=1 $S rehearse2 600 python3 -u bench.py --full --gpus 2 --steps 5 \
         --warmup 2 --no-cpu || exit 99 ;;
     rehearse4)
       # the same at 4 ranks sharing this GPU (one-shots and trees at n = 4)
-      LFA_BENCH_REHEARSE=1 $S rehearse4 900 python3 -u bench.py --gpus 4 --steps 5 \
+      LFA_BENCH_REHEARSE=1 $S rehearse4 900 python3 -u bench.py --full --gpus 4 --steps 5 \
         --warmup 2 --no-cpu --extras-timeout 800 || exit 99 ;;
     rehearse8)
       # the N = 8 flow with its 8 ranks and their 8 isolated extras children
       # on this one GPU (16 processes: the box's limit)
-      LFA_BENCH_REHEARSE=1 $S rehearse8 1100 python3 -u bench.py --gpus 8 --steps 5 \
+      LFA_BENCH_REHEARSE=1 $S rehearse8 1100 python3 -u bench.py --full --gpus 8 --steps 5 \
         --warmup 2 --no-cpu --extras-timeout 900 || exit 99 ;;
     treeputx)
       # the bench extra (fresh buffer sets rotated, median + range)
@@ -153,7 +156,7 @@ for stage in "$@"; do
         --tune-rounds "${TREE_ROUNDS:-8}" || exit 99 ;;
     treeputprof)
       # the tree_put extra under rocprofv3 --kernel-trace --stats
-      $S prof_treeput 300 $P -d gpurun_out/prof_treeput -o run -- python3 bench.py \
+      $S prof_treeput 300 $P -d $OUT/prof_treeput -o run -- python3 bench.py \
         --only-extra tree_put || exit 99 ;;
     treeput5)
       # round-5 forms against the product, 3 buffer sets rotated
@@ -201,11 +204,11 @@ for stage in "$@"; do
       # the fetch / compare tables (256 MiB) and the 32 MiB buckets under
       # --kernel-trace --stats, then FETCH_SIZE and WRITE_SIZE in their own passes
       for x in fetch buckets; do
-        $S "prof_$x" 300 $P -d "gpurun_out/prof_$x" -o run -- python3 bench.py --only-extra $x && \
+        $S "prof_$x" 300 $P -d "$OUT/prof_$x" -o run -- python3 bench.py --only-extra $x && \
         $S "pmc_${x}_fetch" 200 timeout -s KILL 190 rocprofv3 --pmc FETCH_SIZE --output-format csv \
-          -d "gpurun_out/pmc_${x}_fetch" -o run -- python3 bench.py --only-extra $x && \
+          -d "$OUT/pmc_${x}_fetch" -o run -- python3 bench.py --only-extra $x && \
         $S "pmc_${x}_write" 200 timeout -s KILL 190 rocprofv3 --pmc WRITE_SIZE --output-format csv \
-          -d "gpurun_out/pmc_${x}_write" -o run -- python3 bench.py --only-extra $x || exit 99
+          -d "$OUT/pmc_${x}_write" -o run -- python3 bench.py --only-extra $x || exit 99
       done ;;
     *)
       echo "unknown stage $stage"; exit 2 ;;
