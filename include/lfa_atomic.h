@@ -62,6 +62,28 @@ size_t lfa_datatype_size(enum lfa_datatype datatype);
  * table). */
 int lfa_atomic_valid(enum lfa_datatype datatype, enum lfa_op op, uint64_t flags);
 
+/*
+ * What can be REDUCED — by lfa_atomic_write_async / _staged, the tree, tree-put
+ * and one-shot kernels, lfa_host_write / lfa_host_reduce_tree and the
+ * collectives of lfa_coll.h: the write table's 16 columns and, beyond the
+ * reference's tables (which stop at LFA_UINT128), LFA_FLOAT16 and LFA_BFLOAT16.
+ * One pairwise step on those widens both operands to float (exact), applies
+ * the float column's functor and rounds the result to the 16-bit type, round
+ * to nearest even, subnormals kept, overflow to +-inf — after EVERY step, also
+ * inside the fused trees, so every schedule gives the bits of a chain of
+ * pairwise calls.  MIN / MAX return one of the two original 16-bit patterns;
+ * LOR / LAND / LXOR give 1.0 / 0.0.  Their ops are the float column's write
+ * rows: MIN MAX SUM PROD LOR LAND LXOR ATOMIC_WRITE.
+ * lfa_reduce_datatype_size: lfa_datatype_size for the 16 table columns, 2 for
+ *   the two 16-bit floats, else 0 and errno = EINVAL.
+ * lfa_reduce_valid: lfa_atomic_valid(datatype, op, 0) for the table columns;
+ *   0 or -LFA_EOPNOTSUPP for the two 16-bit floats.
+ * The tables below, lfa_datatype_size and lfa_atomic_valid keep the reference's
+ * 16 columns; the fetch and compare tables have no 16-bit float form.
+ */
+size_t lfa_reduce_datatype_size(enum lfa_datatype datatype);
+int lfa_reduce_valid(enum lfa_datatype datatype, enum lfa_op op);
+
 /* Synchronous table form: [op][datatype], NULL where unsupported. */
 extern lfa_write_fn const lfa_atomic_write_handlers[LFA_WRITE_OP_CNT][LFA_DATATYPE_CNT];
 

@@ -32,6 +32,10 @@ def _bind_lfa(L):
     L.lfa_datatype_size.argtypes = [c_int]
     L.lfa_atomic_valid.restype = c_int
     L.lfa_atomic_valid.argtypes = [c_int, c_int, c_uint64]
+    L.lfa_reduce_datatype_size.restype = c_size_t
+    L.lfa_reduce_datatype_size.argtypes = [c_int]
+    L.lfa_reduce_valid.restype = c_int
+    L.lfa_reduce_valid.argtypes = [c_int, c_int]
     L.lfa_atomic_last_error.restype = c_int
     L.lfa_atomic_last_error.argtypes = []
     L.lfa_atomic_write_async.restype = c_int

@@ -9,6 +9,9 @@ Mirrors the reference's L4 combine interface (include/ofi_atomic.h:45-90):
                                     — asynchronous on a HIP stream
   reduce_tree(op, dt, dst, srcs)    prov/coll's log2(N) REDUCE items fused into
                                     one pass (coll_coll.c:349-449 order)
+  reduce_valid / reduce_datatype_size  what write / reduce_tree / the
+                                    collectives take: the table's columns plus
+                                    DT.FLOAT16 and DT.BFLOAT16
 
 Tensors are raw device storage: ``dt`` says how the bytes are interpreted,
 ``cnt`` defaults to ``dst.nbytes // datatype_size(dt)``.  Errors raise
@@ -41,6 +44,19 @@ def atomic_valid(dt: int, op: int, flags: int = 0) -> int:
     return int(lib().lfa_atomic_valid(int(dt), int(op), int(flags)))
 
 
+def reduce_datatype_size(dt: int) -> int:
+    """Element size of what can be reduced: datatype_size for the 16 table
+    columns, 2 for DT.FLOAT16 / DT.BFLOAT16, else 0."""
+    return int(lib().lfa_reduce_datatype_size(int(dt)))
+
+
+def reduce_valid(dt: int, op: int) -> int:
+    """0 where write / reduce_tree / the collectives take (dt, op):
+    atomic_valid(dt, op, 0) for the table columns, the float column's write
+    rows for DT.FLOAT16 / DT.BFLOAT16; else -95."""
+    return int(lib().lfa_reduce_valid(int(dt), int(op)))
+
+
 _FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
 
 
@@ -69,7 +85,7 @@ def write(op: int, dt: int, dst: torch.Tensor, src: torch.Tensor,
     """dst[i] = dst[i] OP src[i] on the GPU (enqueued, not waited for)."""
     _check_dev(dst, "dst")
     _check_dev(src, "src")
-    esz = datatype_size(dt)
+    esz = reduce_datatype_size(dt)
     if cnt is None:
         cnt = dst.nbytes // esz
     if cnt * esz > dst.nbytes or cnt * esz > src.nbytes:
@@ -125,7 +141,7 @@ def reduce_tree(op: int, dt: int, dst: torch.Tensor, srcs: list[torch.Tensor],
     _check_dev(dst, "dst")
     for i, s in enumerate(srcs):
         _check_dev(s, f"srcs[{i}]")
-    esz = datatype_size(dt)
+    esz = reduce_datatype_size(dt)
     if cnt is None:
         cnt = dst.nbytes // esz
     if any(cnt * esz > s.nbytes for s in srcs) or cnt * esz > dst.nbytes:
@@ -143,7 +159,7 @@ def reduce_tree_put(op: int, dt: int, dsts: list[torch.Tensor], srcs: list[torch
     accesses (lfa_reduce_tree_put_async, the LFA_ALGO_P2P kernel)."""
     for i, t in enumerate(list(dsts) + list(srcs)):
         _check_dev(t, f"operand {i}")
-    esz = datatype_size(dt)
+    esz = reduce_datatype_size(dt)
     if cnt is None:
         cnt = dsts[0].nbytes // esz
     if any(cnt * esz > t.nbytes for t in list(dsts) + list(srcs)):
@@ -169,7 +185,7 @@ def _host_ptr(a) -> int:
 def host_write(op: int, dt: int, dst, src, cnt: int | None = None) -> None:
     """dst[i] = dst[i] OP src[i] for HOST buffers (numpy arrays or CPU
     tensors), lfa_host_write: the kernels' functors run on the host."""
-    esz = datatype_size(dt)
+    esz = reduce_datatype_size(dt)
     if cnt is None:
         cnt = dst.nbytes // esz
     rc = lib().lfa_host_write(int(op), int(dt), _host_ptr(dst), _host_ptr(src), cnt)
@@ -179,7 +195,7 @@ def host_write(op: int, dt: int, dst, src, cnt: int | None = None) -> None:
 
 def host_reduce_tree(op: int, dt: int, dst, srcs, cnt: int | None = None) -> None:
     """dst = prov/coll's recursive-doubling tree of HOST buffers srcs."""
-    esz = datatype_size(dt)
+    esz = reduce_datatype_size(dt)
     if cnt is None:
         cnt = dst.nbytes // esz
     arr = (ctypes.c_void_p * len(srcs))(*[_host_ptr(s) for s in srcs])

@@ -106,6 +106,16 @@ constexpr bool in_table(int op, int dt) {
   }
 }
 
+// What the reducing entry points and the collectives take: the write table's
+// members, and FI_FLOAT16 / FI_BFLOAT16 under the float column's write-row
+// ops (lfa_ops.hpp).  The [op][LFA_DATATYPE_CNT] tables, lfa_atomic_valid and
+// lfa_datatype_size keep the reference's 16 columns.
+constexpr bool is_half(int dt) { return dt == LFA_FLOAT16 || dt == LFA_BFLOAT16; }
+constexpr bool reducible(int op, int dt) {
+  if (is_half(dt)) return in_table(op, LFA_FLOAT);
+  return dt >= 0 && dt < LFA_DATATYPE_CNT && in_table(op, dt);
+}
+
 // Fetch table (util_atomic.c:924-950): the write rows plus an ALL-types
 // ATOMIC_READ row; ATOMIC_WRITE is an exchange.
 constexpr bool in_rw_table(int op, int dt) {
@@ -323,10 +333,19 @@ int lfa_atomic_valid(enum lfa_datatype dt, enum lfa_op op, uint64_t flags) {
   return in_table(op, dt) ? 0 : -LFA_EOPNOTSUPP;
 }
 
+size_t lfa_reduce_datatype_size(enum lfa_datatype dt) {
+  if (is_half(dt)) return 2;
+  return lfa_datatype_size(dt);
+}
+
+int lfa_reduce_valid(enum lfa_datatype dt, enum lfa_op op) {
+  if (!is_half(dt)) return lfa_atomic_valid(dt, op, 0);
+  return (unsigned)op < LFA_WRITE_OP_CNT && reducible(op, dt) ? 0 : -LFA_EOPNOTSUPP;
+}
+
 int lfa_atomic_write_async(enum lfa_op op, enum lfa_datatype dt, void *dst,
                            const void *src, size_t cnt, void *stream) {
-  if ((unsigned)op >= LFA_WRITE_OP_CNT || (unsigned)dt >= LFA_DATATYPE_CNT ||
-      !in_table(op, dt))
+  if ((unsigned)op >= LFA_WRITE_OP_CNT || !reducible(op, dt))
     return -LFA_EOPNOTSUPP;
   if (cnt && (!dst || !src)) return -LFA_EINVAL;
   return kWrite[op](dt, dst, src, cnt, stream);
@@ -335,8 +354,7 @@ int lfa_atomic_write_async(enum lfa_op op, enum lfa_datatype dt, void *dst,
 int lfa_reduce_tree_async(enum lfa_op op, enum lfa_datatype dt, void *dst,
                           const void *const *srcs, int nsrc, size_t cnt,
                           void *stream) {
-  if ((unsigned)op > LFA_BXOR || (unsigned)dt >= LFA_DATATYPE_CNT ||
-      !in_table(op, dt))
+  if ((unsigned)op > LFA_BXOR || !reducible(op, dt))
     return -LFA_EOPNOTSUPP;
   if (nsrc < 1 || nsrc > LFA_TREE_MAX || !srcs || (cnt && !dst))
     return -LFA_EINVAL;
@@ -346,7 +364,7 @@ int lfa_reduce_tree_async(enum lfa_op op, enum lfa_datatype dt, void *dst,
   // write table's ATOMIC_WRITE body beats hipMemcpyAsync D2D (83.3 vs 98.8 us
   // at 256 MiB, profiles/r02_probe_copy.log); below, the tree launcher's
   // hipMemcpyAsync stays.
-  const size_t bytes = cnt * lfa_datatype_size(dt);
+  const size_t bytes = cnt * lfa_reduce_datatype_size(dt);
   if (nsrc == 1 && dst != srcs[0] && bytes >= ((size_t)16 << 20))
     return lfa_atomic_write_async(LFA_ATOMIC_WRITE, LFA_UINT8, dst, srcs[0], bytes,
                                   stream);
@@ -356,8 +374,7 @@ int lfa_reduce_tree_async(enum lfa_op op, enum lfa_datatype dt, void *dst,
 int lfa_reduce_tree_put_async(enum lfa_op op, enum lfa_datatype dt,
                               void *const *dsts, int ndst, const void *const *srcs,
                               int nsrc, size_t cnt, void *stream) {
-  if ((unsigned)op > LFA_BXOR || (unsigned)dt >= LFA_DATATYPE_CNT ||
-      !in_table(op, dt))
+  if ((unsigned)op > LFA_BXOR || !reducible(op, dt))
     return -LFA_EOPNOTSUPP;
   if (nsrc < 1 || nsrc > LFA_TREE_MAX || !srcs || ndst < 1 || ndst > LFA_PUT_MAX ||
       !dsts)
@@ -377,8 +394,7 @@ int lfa_atomic_last_error(void) {
 
 int lfa_oneshot_reduce_async(int op, int dt, const struct lfa_oneshot *a,
                                 void *stream) {
-  if ((unsigned)op > LFA_BXOR || (unsigned)dt >= LFA_DATATYPE_CNT ||
-      !in_table(op, dt))
+  if ((unsigned)op > LFA_BXOR || !reducible(op, dt))
     return -LFA_EOPNOTSUPP;
   if (!a) return -LFA_EINVAL;
   return kOneShot[op](dt, a, stream);
@@ -594,12 +610,11 @@ extern "C" {
 
 int lfa_atomic_write_staged(enum lfa_op op, enum lfa_datatype dt, void *dst,
                             const void *src, size_t cnt, size_t chunk_bytes) {
-  if ((unsigned)op >= LFA_WRITE_OP_CNT || (unsigned)dt >= LFA_DATATYPE_CNT ||
-      !in_table(op, dt))
+  if ((unsigned)op >= LFA_WRITE_OP_CNT || !reducible(op, dt))
     return -LFA_EOPNOTSUPP;
   if (cnt && (!dst || !src)) return -LFA_EINVAL;
   if (!cnt) return 0;
-  const size_t esz = lfa_datatype_size(dt);
+  const size_t esz = lfa_reduce_datatype_size(dt);
   if (!chunk_bytes) chunk_bytes = 32u << 20;
   size_t per = chunk_bytes / esz;
   if (!per) per = 1;

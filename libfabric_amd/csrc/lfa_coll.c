@@ -744,6 +744,12 @@ int lfa_coll_ep_flush(struct lfa_coll_ep *ep)
 	       hipStreamSynchronize(ep->d2h_stream) == hipSuccess ? 0 : -LFA_EIO;
 }
 
+/*
+ * LFA_FLOAT16 / LFA_BFLOAT16 are left unmapped on purpose: RCCL's own fp16 /
+ * bf16 reduction does not round to 16 bits after every pairwise step in
+ * prov/coll's order, so LFA_ALGO_RCCL falls back to the tree for them, as for
+ * the other unmapped types.
+ */
 static int rccl_type(enum lfa_datatype dt, ncclDataType_t *t)
 {
 	switch (dt) {
@@ -898,7 +904,7 @@ LFA_INTERNAL int run_device(struct lfa_coll_ep *ep, struct lfa_coll_mc *mc,
 		      enum lfa_op op, hipStream_t s, enum lfa_coll_algo algo)
 {
 	const struct plan *pl;
-	size_t esz = lfa_datatype_size(dt);
+	size_t esz = lfa_reduce_datatype_size(dt);
 	const enum lfa_coll_algo asked = algo;
 	struct xctx x;
 	int ret;
@@ -966,7 +972,7 @@ LFA_INTERNAL int check_reduce_args(enum lfa_datatype dt, enum lfa_op op)
 {
 	if (op < LFA_MIN || op > LFA_BXOR)
 		return -LFA_ENOSYS;   /* coll_process_reduce_item :760-761 */
-	if (lfa_atomic_valid(dt, op, 0))
+	if (lfa_reduce_valid(dt, op))
 		return -LFA_EOPNOTSUPP;
 	return 0;
 }
@@ -1003,7 +1009,7 @@ static ssize_t submit(struct lfa_coll_ep *ep, enum lfa_collective_op coll,
 	mc = mc_of(ep, coll_addr);
 	if (!mc || !mc_member(mc))
 		return -LFA_EINVAL;   /* not a member of this group */
-	esz = lfa_datatype_size(dt);
+	esz = lfa_reduce_datatype_size(dt);
 	if (!esz)
 		return -LFA_EINVAL;
 	if (coll == LFA_REDUCE || coll == LFA_BROADCAST || coll == LFA_SCATTER) {
@@ -1305,10 +1311,14 @@ int lfa_query_collective(struct lfa_coll_domain *domain,
 			return -LFA_ENOSYS;
 		if (flags & LFA_TAGGED)
 			return -LFA_EINVAL;          /* rxm_atomic.c:505-509 */
+		/* flags as ofi_atomic_valid takes them; the plain write form
+		 * also reduces the two 16-bit floats (lfa_reduce_valid) */
 		ret = lfa_atomic_valid(attr->datatype, attr->op, flags);
+		if (ret == -LFA_EOPNOTSUPP && !flags)
+			ret = lfa_reduce_valid(attr->datatype, attr->op);
 		if (ret)
 			return ret;
-		esz = lfa_datatype_size(attr->datatype);
+		esz = lfa_reduce_datatype_size(attr->datatype);
 		attr->datatype_attr.size = esz;
 		/* limited by HBM, not by an eager buffer: 64 GiB per buffer */
 		attr->datatype_attr.count = (size_t)(64ULL << 30) / esz;

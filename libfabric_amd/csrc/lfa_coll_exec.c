@@ -201,7 +201,7 @@ LFA_INTERNAL int sig_barrier(struct xrun *r)
 LFA_INTERNAL int sig_oneshot(struct xrun *r, const struct lfa_step *st)
 {
 	struct lfa_coll_mc *mc = r->mc;
-	size_t esz = lfa_datatype_size(r->dt);
+	size_t esz = lfa_reduce_datatype_size(r->dt);
 	struct lfa_oneshot a;
 	int ret;
 

@@ -584,7 +584,7 @@ LFA_INTERNAL int run_host_chunked(struct lfa_coll_ep *ep, struct lfa_coll_mc *mc
 			    void *result, size_t count, int root,
 			    enum lfa_datatype dt, enum lfa_op op, size_t chunk)
 {
-	size_t esz = lfa_datatype_size(dt), in_slot, idx;
+	size_t esz = lfa_reduce_datatype_size(dt), in_slot, idx;
 	struct lfa_host_chunk c0, c;
 	hipEvent_t h2d[2], comp[2], done[2];
 	int ret, slot = 0;
@@ -661,7 +661,7 @@ LFA_INTERNAL int run_device_chunked(struct lfa_coll_ep *ep, struct lfa_coll_mc *
 		return run_host_chunked(ep, mc, coll, buf, result, count, root, dt, op,
 					chunk);
 	for (size_t idx = 0; !ret &&
-	     lfa_coll_host_chunk(coll, count, mc->size, lfa_datatype_size(dt), chunk, idx,
+	     lfa_coll_host_chunk(coll, count, mc->size, lfa_reduce_datatype_size(dt), chunk, idx,
 				 &c) == 1; idx++)
 		ret = run_device(ep, mc, coll, buf ? (const char *)buf + c.src_off : NULL,
 				 result ? (char *)result + c.dst_off : NULL, c.dev_count,
@@ -703,7 +703,7 @@ LFA_INTERNAL int host_start(struct lfa_coll_ep *ep, struct hop *h,
 		      enum lfa_datatype dt, enum lfa_op op, int dev,
 		      enum lfa_coll_algo algo)
 {
-	size_t esz = lfa_datatype_size(dt);
+	size_t esz = lfa_reduce_datatype_size(dt);
 	/* this operation's sequence number, taken before a P2P handshake below
 	 * draws the next ones */
 	const uint16_t seq = (uint16_t)(mc->seq - 1);
@@ -896,7 +896,7 @@ LFA_INTERNAL int peer_submit_chunked(struct lfa_coll_ep *ep, struct lfa_coll_mc 
 			       enum lfa_datatype dt, enum lfa_op op, void *context,
 			       int dev, size_t chunk)
 {
-	const size_t esz = lfa_datatype_size(dt);
+	const size_t esz = lfa_reduce_datatype_size(dt);
 	const uint64_t chain = ++ep->next_chain;
 	size_t per = chunk / esz;
 	int ret;

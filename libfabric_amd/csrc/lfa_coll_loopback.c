@@ -26,7 +26,7 @@ int lfa_coll_loopback(enum lfa_collective_op coll, enum lfa_coll_algo algo,
 		      void *stream)
 {
 	hipStream_t s = (hipStream_t)stream;
-	size_t esz = lfa_datatype_size(dt);
+	size_t esz = lfa_reduce_datatype_size(dt);
 	struct plan *pl = NULL;
 	size_t *pc = NULL, *arrived = NULL, region = sym_region(count, esz);
 	void **tmp = NULL;

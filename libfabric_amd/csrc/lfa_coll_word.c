@@ -292,10 +292,10 @@ LFA_INTERNAL int run_solo(struct lfa_coll_ep *ep, const void *buf, void *result,
 	int ret;
 
 	ep->op_done_w = NULL;
-	if (ep->allow_direct && count * lfa_datatype_size(dt) <= LFA_DIRECT_SOLO_BYTES &&
+	if (ep->allow_direct && count * lfa_reduce_datatype_size(dt) <= LFA_DIRECT_SOLO_BYTES &&
 	    direct_of(ep) && !lfa_direct_failed(ep->direct)) {
 		/* no HIP launch: ~3 us less host time */
-		ret = lfa_direct_solo_copy(ep->direct, result, buf, count * lfa_datatype_size(dt),
+		ret = lfa_direct_solo_copy(ep->direct, result, buf, count * lfa_reduce_datatype_size(dt),
 					   ep->ddone_ctr, ep->ddone_word, ep->ddone_seq + 1);
 		if (!ret) {
 			ep->op_done_val = ++ep->ddone_seq;
@@ -311,7 +311,7 @@ LFA_INTERNAL int run_solo(struct lfa_coll_ep *ep, const void *buf, void *result,
 	/* the one-shot kernel with n = 1 gives the same bytes; this kernel's
 	 * arguments are 48 bytes instead of ~700, about 1 us less from launch
 	 * to the word (tools/probe_solo_latency.py) */
-	ret = lfa_solo_copy_async(result, buf, count * lfa_datatype_size(dt), ep->done_ctr,
+	ret = lfa_solo_copy_async(result, buf, count * lfa_reduce_datatype_size(dt), ep->done_ctr,
 				  ep->done_word, ep->done_seq + 1, ep->stream);
 	if (ret)
 		return ret;

@@ -80,6 +80,22 @@ static int by_type(int dt, F &&f) {
   }
 }
 
+// The reducing entry points (write, tree, tree-put, one-shot) also take
+// FI_FLOAT16 / FI_BFLOAT16 (lfa_reduce_valid); the fetch and compare tables
+// do not.  ATOMIC_WRITE moves 16-bit patterns: the uint16_t kernels.
+template <int OP, typename F>
+static int by_reduce_type(int dt, F &&f) {
+  switch (dt) {
+    case LFA_FLOAT16:
+      if constexpr (OP == OP_WRITE) return f((uint16_t *)0);
+      else return f((f16 *)0);
+    case LFA_BFLOAT16:
+      if constexpr (OP == OP_WRITE) return f((uint16_t *)0);
+      else return f((bf16 *)0);
+    default: return by_type<OP>(dt, f);
+  }
+}
+
 }  // namespace lfa
 
 #ifndef LFA_OP
@@ -96,7 +112,7 @@ extern "C" int LFA_CAT(lfa__write_op, LFA_OP)(int dt, void *dst,
                                               void *stream) {
   // dt | LFA_WRITE_MAPPED: operands on their host mappings (lfa_capi.cpp)
   const bool mapped = (dt & LFA_WRITE_MAPPED) != 0;
-  return lfa::by_type<LFA_OP>(dt & ~LFA_WRITE_MAPPED, [&](auto *tag) {
+  return lfa::by_reduce_type<LFA_OP>(dt & ~LFA_WRITE_MAPPED, [&](auto *tag) {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     return lfa::launch_write<LFA_OP, T>(dst, src, cnt, (hipStream_t)stream, mapped);
   });
@@ -107,7 +123,7 @@ extern "C" int LFA_CAT(lfa__write_op, LFA_OP)(int dt, void *dst,
 extern "C" int LFA_CAT(lfa__tree_op, LFA_OP)(int dt, void *dst,
                                              const void *const *srcs, int nsrc,
                                              size_t cnt, void *stream) {
-  return lfa::by_type<LFA_OP>(dt, [&](auto *tag) {
+  return lfa::by_reduce_type<LFA_OP>(dt, [&](auto *tag) {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     return lfa::launch_tree<LFA_OP, T>(dst, srcs, nsrc, cnt,
                                        (hipStream_t)stream);
@@ -116,7 +132,7 @@ extern "C" int LFA_CAT(lfa__tree_op, LFA_OP)(int dt, void *dst,
 
 extern "C" int LFA_CAT(lfa__oneshot_op, LFA_OP)(int dt, const lfa_oneshot *a,
                                                 void *stream) {
-  return lfa::by_type<LFA_OP>(dt, [&](auto *tag) {
+  return lfa::by_reduce_type<LFA_OP>(dt, [&](auto *tag) {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     return lfa::launch_oneshot<LFA_OP, T>(*a, (hipStream_t)stream);
   });
@@ -125,7 +141,7 @@ extern "C" int LFA_CAT(lfa__oneshot_op, LFA_OP)(int dt, const lfa_oneshot *a,
 extern "C" int LFA_CAT(lfa__treeput_op, LFA_OP)(int dt, void *const *dsts, int ndst,
                                                 const void *const *srcs, int nsrc,
                                                 size_t cnt, void *stream) {
-  return lfa::by_type<LFA_OP>(dt, [&](auto *tag) {
+  return lfa::by_reduce_type<LFA_OP>(dt, [&](auto *tag) {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     return lfa::launch_tree_put<LFA_OP, T>(dsts, ndst, srcs, nsrc, cnt,
                                            (hipStream_t)stream);

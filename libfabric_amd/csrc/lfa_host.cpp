@@ -146,6 +146,17 @@ int by_type(int dt, F &&f) {
   }
 }
 
+// lfa_host_write / lfa_host_reduce_tree also take FI_FLOAT16 / FI_BFLOAT16
+// (lfa_reduce_valid); the fetch and compare forms do not.
+template <typename F>
+int by_reduce_type(int dt, F &&f) {
+  switch (dt) {
+    case LFA_FLOAT16: return f((f16 *)0);
+    case LFA_BFLOAT16: return f((bf16 *)0);
+    default: return by_type(dt, f);
+  }
+}
+
 template <typename F>
 int by_op(int op, F &&f) {
   switch (op) {
@@ -186,12 +197,12 @@ extern "C" {
 
 int lfa_host_write(enum lfa_op op, enum lfa_datatype dt, void *dst, const void *src,
                    size_t cnt) {
-  if (lfa_atomic_valid(dt, op, 0)) return -LFA_EOPNOTSUPP;
+  if (lfa_reduce_valid(dt, op)) return -LFA_EOPNOTSUPP;
   if (cnt && (!dst || !src)) return -LFA_EINVAL;
   return lfa::by_op(op, [&](auto opc) {
     constexpr int OP = decltype(opc)::value;
     if constexpr (OP == lfa::OP_READ) return -LFA_EOPNOTSUPP;
-    else return lfa::by_type(dt, [&](auto *tag) {
+    else return lfa::by_reduce_type(dt, [&](auto *tag) {
       typedef typename std::remove_pointer<decltype(tag)>::type T;
       return lfa::host_write<OP, T>(dst, src, cnt);
     });
@@ -226,18 +237,18 @@ int lfa_host_swap(enum lfa_op op, enum lfa_datatype dt, void *dst, const void *s
 
 int lfa_host_reduce_tree(enum lfa_op op, enum lfa_datatype dt, void *dst,
                          const void *const *srcs, int nsrc, size_t cnt) {
-  if ((unsigned)op > LFA_BXOR || lfa_atomic_valid(dt, op, 0)) return -LFA_EOPNOTSUPP;
+  if ((unsigned)op > LFA_BXOR || lfa_reduce_valid(dt, op)) return -LFA_EOPNOTSUPP;
   if (nsrc < 1 || nsrc > LFA_TREE_MAX || !srcs || (cnt && !dst)) return -LFA_EINVAL;
   for (int k = 0; k < nsrc; k++)
     if (cnt && !srcs[k]) return -LFA_EINVAL;
   if (!cnt) return 0;
   if (nsrc == 1) {
-    if (dst != srcs[0]) memmove(dst, srcs[0], cnt * lfa_datatype_size(dt));
+    if (dst != srcs[0]) memmove(dst, srcs[0], cnt * lfa_reduce_datatype_size(dt));
     return 0;
   }
   return lfa::by_op(op, [&](auto opc) {
     constexpr int OP = decltype(opc)::value;
-    return lfa::by_type(dt, [&](auto *tag) {
+    return lfa::by_reduce_type(dt, [&](auto *tag) {
       typedef typename std::remove_pointer<decltype(tag)>::type T;
       return lfa::host_tree<OP, T>(dst, srcs, nsrc, cnt);
     });

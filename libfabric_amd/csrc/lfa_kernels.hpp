@@ -50,9 +50,56 @@ __device__ __forceinline__ unsigned wave_id() {
   else return threadIdx.x / 64;
 }
 
+// Two 16-bit floats per dword (lfa_ops.hpp: widen, float op, round to nearest
+// even after every step).  bf16 widens with a shift and a mask, operates in
+// float and packs both results with gfx950's v_cvt_pk_bf16_f32 (round to
+// nearest even, subnormals kept: the kernels run with denormals on).  fp16
+// SUM / PROD are one packed-f16 instruction: the same bits as the float
+// route, as 24 >= 2·11 + 2 makes the double rounding innocuous.  MIN / MAX
+// compare the values and select the ORIGINAL halves — never v_min / v_max,
+// whose NaN rule is not the dst-biased compare's.
+typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 b16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+template <int OP>
+constexpr bool half_vec_op() {
+  return OP == OP_MIN || OP == OP_MAX || OP == OP_SUM || OP == OP_PROD;
+}
+
+template <int OP, typename T>
+__device__ __forceinline__ uint32_t half_pair(uint32_t d, uint32_t s) {
+  bool tl, th;  // MIN / MAX: take src's low / high half
+  if constexpr (__is_same(T, bf16)) {
+    const float dl = bits_float(d << 16), dh = bits_float(d & 0xffff0000u);
+    const float sl = bits_float(s << 16), sh = bits_float(s & 0xffff0000u);
+    if constexpr (OP == OP_SUM)
+      return __builtin_bit_cast(uint32_t,
+                                __builtin_convertvector(f32x2{dl + sl, dh + sh}, b16x2));
+    if constexpr (OP == OP_PROD)
+      return __builtin_bit_cast(uint32_t,
+                                __builtin_convertvector(f32x2{dl * sl, dh * sh}, b16x2));
+    tl = OP == OP_MIN ? dl > sl : dl < sl;
+    th = OP == OP_MIN ? dh > sh : dh < sh;
+  } else {
+    const h16x2 a = __builtin_bit_cast(h16x2, d), b = __builtin_bit_cast(h16x2, s);
+    if constexpr (OP == OP_SUM) return __builtin_bit_cast(uint32_t, a + b);
+    if constexpr (OP == OP_PROD) return __builtin_bit_cast(uint32_t, a * b);
+    tl = OP == OP_MIN ? a.x > b.x : a.x < b.x;
+    th = OP == OP_MIN ? a.y > b.y : a.y < b.y;
+  }
+  return ((tl ? s : d) & 0xffffu) | ((th ? s : d) & 0xffff0000u);
+}
+
 // OP applied lane-wise to the 16/sizeof(T) elements packed in a 16-B vector.
 template <int OP, typename T>
 __device__ __forceinline__ u32x4 apply_vec(u32x4 d, u32x4 s) {
+  if constexpr (IsHalf<T>::value && half_vec_op<OP>()) {
+    u32x4 r;
+#pragma unroll
+    for (int i = 0; i < 4; i++) r[i] = half_pair<OP, T>(d[i], s[i]);
+    return r;
+  }
   constexpr int N = 16 / sizeof(T);
   T a[N], b[N];
   __builtin_memcpy(a, &d, 16);

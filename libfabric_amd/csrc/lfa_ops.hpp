@@ -145,10 +145,115 @@ LFA_HD cf32 mul<cf32>(cf32 x, cf32 y) {
   return cf32{re, im};
 }
 
+// ---------------------------------------------------------------------------
+// FI_FLOAT16 / FI_BFLOAT16 (no column in util_atomic.c: its tables stop at
+// FI_UINT128).  Storage is the 16-bit pattern.  One pairwise step widens both
+// operands to float (exact), applies the float functor and rounds the result
+// back to 16 bits, round-to-nearest-even, subnormals kept, overflow to ±inf —
+// after EVERY step, also inside the fused trees, so every schedule equals a
+// chain of pairwise calls bit for bit.  MIN / MAX return one of the two
+// original patterns.  NaN results are some NaN (payload and sign not defined).
+// ---------------------------------------------------------------------------
+struct f16 { uint16_t bits; };   // IEEE binary16
+struct bf16 { uint16_t bits; };  // bfloat16: the high half of a float
+
+template <typename T> struct IsHalf { static constexpr bool value = false; };
+template <> struct IsHalf<f16> { static constexpr bool value = true; };
+template <> struct IsHalf<bf16> { static constexpr bool value = true; };
+
+// truth is `v != 0` on the value: -0 is false, NaN is true
+template <>
+LFA_HD bool truth<f16>(f16 v) { return (v.bits & 0x7fffu) != 0; }
+template <>
+LFA_HD bool truth<bf16>(bf16 v) { return (v.bits & 0x7fffu) != 0; }
+template <>
+LFA_HD f16 from_bool<f16>(bool b) { return f16{(uint16_t)(b ? 0x3c00u : 0u)}; }
+template <>
+LFA_HD bf16 from_bool<bf16>(bool b) { return bf16{(uint16_t)(b ? 0x3f80u : 0u)}; }
+
+LFA_HD float bits_float(uint32_t u) {
+  float f;
+  __builtin_memcpy(&f, &u, 4);
+  return f;
+}
+LFA_HD uint32_t float_bits(float f) {
+  uint32_t u;
+  __builtin_memcpy(&u, &f, 4);
+  return u;
+}
+
+LFA_HD float widen(bf16 v) { return bits_float((uint32_t)v.bits << 16); }
+LFA_HD float widen(f16 v) {
+#ifdef __HIP_DEVICE_COMPILE__
+  _Float16 h;
+  __builtin_memcpy(&h, &v.bits, 2);
+  return (float)h;
+#else
+  const uint32_t h = v.bits, sign = (h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
+  if (e == 0)  // zero or subnormal: m · 2^-24, exact in float
+    return bits_float(sign | float_bits((float)m * 0x1p-24f));
+  if (e == 31) return bits_float(sign | 0x7f800000u | (m << 13));
+  return bits_float(sign | ((e + 112u) << 23) | (m << 13));
+#endif
+}
+
+template <typename T> LFA_HD T narrow(float f);
+template <>
+LFA_HD bf16 narrow<bf16>(float f) {
+  const uint32_t u = float_bits(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return bf16{(uint16_t)((u >> 16) | 0x40u)};
+  return bf16{(uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16)};
+}
+template <>
+LFA_HD f16 narrow<f16>(float f) {
+#ifdef __HIP_DEVICE_COMPILE__
+  const _Float16 h = (_Float16)f;
+  f16 r;
+  __builtin_memcpy(&r.bits, &h, 2);
+  return r;
+#else
+  const uint32_t x = float_bits(f), sign = (x >> 16) & 0x8000u;
+  uint32_t a = x & 0x7fffffffu;
+  if (a >= 0x47800000u)  // >= 2^16, inf or NaN
+    return f16{(uint16_t)(sign | (a > 0x7f800000u ? 0x7e00u : 0x7c00u))};
+  if (a < 0x38800000u) {
+    // below the smallest normal (2^-14): adding 0.5 puts the float's last
+    // place at 2^-24, the subnormal step, and the adder rounds to even
+    a = float_bits(bits_float(a) + 0.5f) - 0x3f000000u;
+    return f16{(uint16_t)(sign | a)};
+  }
+  a += 0xc8000000u + 0xfffu + ((a >> 13) & 1u);  // rebias by -112, round to even
+  return f16{(uint16_t)(sign | (a >> 13))};      // a carry out of 0x7bff is inf
+#endif
+}
+
+template <int OP, typename T>
+LFA_HD T half_apply(T d, T s) {
+  if constexpr (OP == OP_MIN) {
+    return (widen(d) > widen(s)) ? s : d;
+  } else if constexpr (OP == OP_MAX) {
+    return (widen(d) < widen(s)) ? s : d;
+  } else if constexpr (OP == OP_SUM) {
+    return narrow<T>(widen(d) + widen(s));
+  } else if constexpr (OP == OP_PROD) {
+    return narrow<T>(widen(d) * widen(s));
+  } else if constexpr (OP == OP_LOR) {
+    return from_bool<T>(truth(d) || truth(s));
+  } else if constexpr (OP == OP_LAND) {
+    return from_bool<T>(truth(d) && truth(s));
+  } else if constexpr (OP == OP_LXOR) {
+    return from_bool<T>(truth(d) != truth(s));
+  } else {  // OP_WRITE (the bitwise rows are not supported<>)
+    return s;
+  }
+}
+
 // d OP s for one element.  OP is an enum fi_op value.
 template <int OP, typename T>
 LFA_HD T apply(T d, T s) {
-  if constexpr (OP == OP_MIN) {
+  if constexpr (IsHalf<T>::value) {
+    return half_apply<OP, T>(d, s);
+  } else if constexpr (OP == OP_MIN) {
     return (d > s) ? s : d;
   } else if constexpr (OP == OP_MAX) {
     return (d < s) ? s : d;
@@ -183,6 +288,14 @@ template <typename T> struct Class {
 template <> struct Class<cf32> {
   static constexpr bool is_int = false;
   static constexpr bool is_complex = true;
+};
+template <> struct Class<f16> {  // the float column's rows
+  static constexpr bool is_int = false;
+  static constexpr bool is_complex = false;
+};
+template <> struct Class<bf16> {
+  static constexpr bool is_int = false;
+  static constexpr bool is_complex = false;
 };
 
 template <int OP, typename T>

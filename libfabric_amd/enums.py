@@ -24,6 +24,10 @@ class DT(enum.IntEnum):
     LONG_DOUBLE_COMPLEX = 13
     INT128 = 14
     UINT128 = 15
+    # beyond the reference's tables: reducible (atomic.reduce_valid), no
+    # column in the [op][16] tables
+    FLOAT16 = 16
+    BFLOAT16 = 17
 
 
 class OP(enum.IntEnum):
@@ -56,7 +60,8 @@ class COLL(enum.IntEnum):
 SIZES = {DT.INT8: 1, DT.UINT8: 1, DT.INT16: 2, DT.UINT16: 2, DT.INT32: 4,
          DT.UINT32: 4, DT.INT64: 8, DT.UINT64: 8, DT.FLOAT: 4, DT.DOUBLE: 8,
          DT.FLOAT_COMPLEX: 8, DT.DOUBLE_COMPLEX: 16, DT.LONG_DOUBLE: 16,
-         DT.LONG_DOUBLE_COMPLEX: 32, DT.INT128: 16, DT.UINT128: 16}
+         DT.LONG_DOUBLE_COMPLEX: 32, DT.INT128: 16, DT.UINT128: 16,
+         DT.FLOAT16: 2, DT.BFLOAT16: 2}
 
 _TORCH = {
     torch.int8: DT.INT8, torch.uint8: DT.UINT8, torch.int16: DT.INT16,
@@ -64,6 +69,7 @@ _TORCH = {
     torch.int64: DT.INT64, torch.uint64: DT.UINT64, torch.float32: DT.FLOAT,
     torch.float64: DT.DOUBLE, torch.complex64: DT.FLOAT_COMPLEX,
     torch.complex128: DT.DOUBLE_COMPLEX,
+    torch.float16: DT.FLOAT16, torch.bfloat16: DT.BFLOAT16,
 }
 _TORCH_INV = {v: k for k, v in _TORCH.items()}
 
