@@ -134,6 +134,61 @@ int lfa_reduce_tree_put_async(enum lfa_op op, enum lfa_datatype datatype,
 			      int nsrc, size_t cnt, void *stream);
 
 /*
+ * The list forms: what fi_atomicv / fi_atomicmsg hand a provider, an array of
+ * struct fi_ioc (= struct lfa_ioc), combined in ONE launch instead of one per
+ * entry.
+ * lfa_atomic_writev_async: for every segment i,
+ *     dst[i].addr[j] = dst[i].addr[j] OP src[i].addr[j]   for j < dst[i].count
+ *   — bit for bit what nseg calls of lfa_atomic_write_async give.
+ * lfa_reduce_treev_async: dst[i] = tree(srcs[i*nsrc + 0], ..., srcs[i*nsrc +
+ *   nsrc-1]) over dst[i].count elements — what nseg calls of
+ *   lfa_reduce_tree_async give; `srcs` is a HOST array of nseg*nsrc DEVICE
+ *   pointers, row-major [nseg][nsrc]; dst[i] may alias any of its own
+ *   srcs[i][k].  One launch for 1 <= nsrc <= 15.  Limitation: from 16 inputs
+ *   the call enqueues one tree launch per segment (the same result; the
+ *   16- and 32-leaf bodies are not built for the list form).
+ * Every (op, datatype) lfa_reduce_valid accepts; counts are in elements.
+ * Segments may have any byte alignment, each independent of the others: every
+ * segment takes the vector, element or byte-wise path its own alignment
+ * permits.  A segment with count 0 is skipped; nseg == 0 returns 0 and
+ * launches nothing.  `dst`, `src` and `srcs` are HOST arrays of DEVICE
+ * addresses.  The calls are asynchronous: when they return the caller may
+ * overwrite or free the arrays (not the buffers).  No hipMalloc and no
+ * blocking synchronisation in steady state: a small segment table travels in
+ * the kernel arguments, a larger one through a ring of reused device slots
+ * ordered on `stream` (a call waits for the oldest slot's launch only when
+ * more than the ring holds are in flight).
+ * Inputs and other segments: only the dst ranges are checked against each
+ * other.  A src[i] or srcs[i][k] must not overlap dst[j] for j != i: separate
+ * launches would order that read against that write, one kernel does not, and
+ * the result of such a list is undefined (no error is reported).
+ * Graph capture: a call whose table travels in the kernel arguments (at most
+ * 64 words: (nseg + 2) / 2 + nseg * (2 + inputs), e.g. 18 writev segments)
+ * may be captured.  A larger table must not be issued on a capturing stream:
+ * the ring path queries and may wait on an event of `stream`, and a replay
+ * would copy whatever the reused pinned slot then holds.  While one caller
+ * waits for the oldest slot, other threads' ring-path calls on that device
+ * wait behind it.
+ * Errors, all reported before anything is enqueued (one exception: with
+ * nsrc >= 16, a HIP failure at segment i is returned after segments 0..i-1
+ * were enqueued):
+ *   -LFA_EOPNOTSUPP  lfa_reduce_valid refuses (datatype, op)
+ *   -LFA_EINVAL      a NULL array; a NULL addr with a non-zero count;
+ *                    src[i].count != dst[i].count; nseg > LFA_IOV_MAX; nsrc
+ *                    outside 1..LFA_TREE_MAX; two dst segments whose byte
+ *                    ranges overlap (separate launches would order them, one
+ *                    kernel cannot)
+ *   -LFA_EIO         a HIP failure
+ *   -LFA_ENOMEM      a ring slot could not be allocated or grown
+ */
+int lfa_atomic_writev_async(enum lfa_op op, enum lfa_datatype datatype,
+			    const struct lfa_ioc *dst, const struct lfa_ioc *src,
+			    size_t nseg, void *stream);
+int lfa_reduce_treev_async(enum lfa_op op, enum lfa_datatype datatype,
+			   const struct lfa_ioc *dst, const void *const *srcs,
+			   int nsrc, size_t nseg, void *stream);
+
+/*
  * Fetch table — replaces ofi_atomic_readwrite_handlers (util_atomic.c:924-950):
  * res[i] = dst[i], then dst[i] = dst[i] OP src[i] (ATOMIC_READ: load only,
  * ATOMIC_WRITE: exchange).
@@ -194,6 +249,11 @@ int lfa_host_write(enum lfa_op op, enum lfa_datatype datatype, void *dst,
 		   const void *src, size_t cnt);
 int lfa_host_reduce_tree(enum lfa_op op, enum lfa_datatype datatype, void *dst,
 			 const void *const *srcs, int nsrc, size_t cnt);
+/* lfa_host_writev: the list form on host memory, what nseg calls of
+ * lfa_host_write give; arguments and errors as lfa_atomic_writev_async. */
+int lfa_host_writev(enum lfa_op op, enum lfa_datatype datatype,
+		    const struct lfa_ioc *dst, const struct lfa_ioc *src,
+		    size_t nseg);
 /* Fetch and compare tables on host memory (res = old dst, as the
  * readwrite / swap handlers, util_atomic.c:924-980). */
 int lfa_host_readwrite(enum lfa_op op, enum lfa_datatype datatype, void *dst,

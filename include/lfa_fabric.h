@@ -135,6 +135,17 @@ struct lfa_collective_attr {
 	uint64_t mode;
 };
 
+/* Mirrors struct fi_ioc, include/rdma/fabric.h:193-196: one segment of a
+ * list-form atomic (fi_atomicv / fi_atomicmsg); `count` is in ELEMENTS of the
+ * call's datatype.  Same layout, so a caller's fi_ioc array passes through. */
+struct lfa_ioc {
+	void *addr;
+	size_t count;
+};
+
+/* Most segments one list-form call takes (lfa_atomic.h). */
+#define LFA_IOV_MAX 4096
+
 #ifdef __cplusplus
 }
 #endif

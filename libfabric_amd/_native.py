@@ -25,6 +25,14 @@ def lib_path(name: str = "lfa") -> str:
     return os.path.join(PKG, _LIBS[name])
 
 
+class lfa_ioc(ctypes.Structure):
+    """struct lfa_ioc (= struct fi_ioc): one segment of a list-form call."""
+    _fields_ = [("addr", ctypes.c_void_p), ("count", ctypes.c_size_t)]
+
+
+LFA_IOV_MAX = 4096
+
+
 def _bind_lfa(L):
     c_int, c_size_t, c_void_p, c_uint64 = (ctypes.c_int, ctypes.c_size_t,
                                            ctypes.c_void_p, ctypes.c_uint64)
@@ -62,6 +70,14 @@ def _bind_lfa(L):
     L.lfa_host_small_bytes.restype = c_size_t
     L.lfa_host_write.restype = c_int
     L.lfa_host_write.argtypes = [c_int, c_int, c_void_p, c_void_p, c_size_t]
+    ioc_p = ctypes.POINTER(lfa_ioc)
+    L.lfa_atomic_writev_async.restype = c_int
+    L.lfa_atomic_writev_async.argtypes = [c_int, c_int, ioc_p, ioc_p, c_size_t, c_void_p]
+    L.lfa_reduce_treev_async.restype = c_int
+    L.lfa_reduce_treev_async.argtypes = [c_int, c_int, ioc_p, ctypes.POINTER(c_void_p),
+                                         c_int, c_size_t, c_void_p]
+    L.lfa_host_writev.restype = c_int
+    L.lfa_host_writev.argtypes = [c_int, c_int, ioc_p, ioc_p, c_size_t]
     L.lfa_host_reduce_tree.restype = c_int
     L.lfa_host_reduce_tree.argtypes = [c_int, c_int, c_void_p, ctypes.POINTER(c_void_p),
                                        c_int, c_size_t]

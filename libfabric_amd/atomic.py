@@ -9,6 +9,9 @@ Mirrors the reference's L4 combine interface (include/ofi_atomic.h:45-90):
                                     — asynchronous on a HIP stream
   reduce_tree(op, dt, dst, srcs)    prov/coll's log2(N) REDUCE items fused into
                                     one pass (coll_coll.c:349-449 order)
+  writev / reduce_treev / host_writev  the fi_ioc (list) forms of write /
+                                    reduce_tree / host_write: every segment of
+                                    a list in one launch (fi_atomicv's shape)
   reduce_valid / reduce_datatype_size  what write / reduce_tree / the
                                     collectives take: the table's columns plus
                                     DT.FLOAT16 and DT.BFLOAT16
@@ -23,7 +26,7 @@ import ctypes
 
 import torch
 
-from ._native import lib
+from ._native import LFA_IOV_MAX, lfa_ioc, lib  # noqa: F401  (re-exported)
 from .enums import DT, OP
 
 LFA_EOPNOTSUPP = 95
@@ -170,6 +173,78 @@ def reduce_tree_put(op: int, dt: int, dsts: list[torch.Tensor], srcs: list[torch
                                          cnt, _stream_handle(stream))
     if rc:
         raise LfaError(rc, f"lfa_reduce_tree_put_async({OP(op).name},{DT(dt).name})")
+
+
+# ------------------------------------------------------------- list forms --
+
+def _ioc_array(ptrs: list[int], counts: list[int]):
+    arr = (lfa_ioc * max(len(ptrs), 1))()
+    for i, (p, n) in enumerate(zip(ptrs, counts)):
+        arr[i].addr = p
+        arr[i].count = n
+    return arr
+
+
+def _seg_counts(dsts, esz: int) -> list[int]:
+    return [d.nbytes // esz for d in dsts]
+
+
+def writev(op: int, dt: int, dsts: list[torch.Tensor], srcs: list[torch.Tensor],
+           stream=None) -> None:
+    """dsts[i] = dsts[i] OP srcs[i] for every i in ONE launch
+    (lfa_atomic_writev_async, the fi_ioc form of ``write``).  Segment i has
+    dsts[i].nbytes // size(dt) elements; srcs[i] must hold as many."""
+    if len(dsts) != len(srcs):
+        raise ValueError("dsts and srcs differ in length")
+    for i, (d, s) in enumerate(zip(dsts, srcs)):
+        _check_dev(d, f"dsts[{i}]")
+        _check_dev(s, f"srcs[{i}]")
+    esz = reduce_datatype_size(dt)
+    da = _ioc_array([d.data_ptr() for d in dsts], _seg_counts(dsts, esz) if esz else [])
+    sa = _ioc_array([s.data_ptr() for s in srcs], _seg_counts(srcs, esz) if esz else [])
+    rc = lib().lfa_atomic_writev_async(int(op), int(dt), da, sa, len(dsts),
+                                       _stream_handle(stream))
+    if rc:
+        raise LfaError(rc, f"lfa_atomic_writev_async({OP(op).name},{DT(dt).name})")
+
+
+def reduce_treev(op: int, dt: int, dsts: list[torch.Tensor],
+                 srcs: list[list[torch.Tensor]], stream=None) -> None:
+    """dsts[i] = recursive-doubling tree of srcs[i] for every i in ONE launch
+    (lfa_reduce_treev_async); every srcs[i] has the same length, and dsts[i]
+    may be one of its own srcs[i]."""
+    if len(dsts) != len(srcs):
+        raise ValueError("dsts and srcs differ in length")
+    nsrc = len(srcs[0]) if srcs else 1
+    esz = reduce_datatype_size(dt)
+    for i, (d, row) in enumerate(zip(dsts, srcs)):
+        if len(row) != nsrc:
+            raise ValueError("every segment needs the same number of inputs")
+        _check_dev(d, f"dsts[{i}]")
+        for k, s in enumerate(row):
+            _check_dev(s, f"srcs[{i}][{k}]")
+            if s.nbytes < d.nbytes:
+                raise ValueError(f"srcs[{i}][{k}] is shorter than dsts[{i}]")
+    da = _ioc_array([d.data_ptr() for d in dsts], _seg_counts(dsts, esz) if esz else [])
+    flat = [s.data_ptr() for row in srcs for s in row]
+    sa = (ctypes.c_void_p * max(len(flat), 1))(*flat)
+    rc = lib().lfa_reduce_treev_async(int(op), int(dt), da, sa, nsrc, len(dsts),
+                                      _stream_handle(stream))
+    if rc:
+        raise LfaError(rc, f"lfa_reduce_treev_async({OP(op).name},{DT(dt).name})")
+
+
+def host_writev(op: int, dt: int, dsts, srcs) -> None:
+    """The list form on HOST buffers (numpy arrays or CPU tensors):
+    lfa_host_writev, what one host_write per segment gives."""
+    if len(dsts) != len(srcs):
+        raise ValueError("dsts and srcs differ in length")
+    esz = reduce_datatype_size(dt)
+    da = _ioc_array([_host_ptr(d) for d in dsts], _seg_counts(dsts, esz) if esz else [])
+    sa = _ioc_array([_host_ptr(s) for s in srcs], _seg_counts(srcs, esz) if esz else [])
+    rc = lib().lfa_host_writev(int(op), int(dt), da, sa, len(dsts))
+    if rc:
+        raise LfaError(rc, f"lfa_host_writev({op},{dt})")
 
 
 # ------------------------------------------------------- host-memory forms --

@@ -52,6 +52,7 @@ def build_lfa(jobs: int = 8, verbose: bool = False) -> str:
     os.makedirs(BUILD, exist_ok=True)
     kern = os.path.join(CSRC, "lfa_combine.hip")
     hdrs = [os.path.join(CSRC, "lfa_ops.hpp"), os.path.join(CSRC, "lfa_kernels.hpp"),
+            os.path.join(CSRC, "lfa_k_iov.hpp"), os.path.join(CSRC, "lfa_iov.h"),
             *(os.path.join(CSRC, f"lfa_k_{p}.hpp") for p in ("tree", "oneshot", "fetch", "launch")),
             os.path.join(INC, "lfa_atomic.h"), os.path.join(INC, "lfa_fabric.h")]
     steps = []

@@ -38,6 +38,8 @@ namespace lfa {
 // ~100 (op, datatype) kernel families build in parallel; each object exports
 //   lfa__write_op<N>(dt, dst, src, cnt, stream)
 //   lfa__tree_op<N>(dt, dst, srcs, nsrc, cnt, stream)
+//   lfa__writev_op<N>(dt, args, ntile, stream)
+//   lfa__treev_op<N>(dt, args, nsrc, ntile, stream)
 // which lfa_capi.cpp dispatches to.  Return 0 or a negative LFA_E* code.
 // Ops whose result bits do not depend on an integer's signedness: wrapping
 // SUM / PROD (the low bits of a two's-complement sum or product), the
@@ -96,6 +98,25 @@ static int by_reduce_type(int dt, F &&f) {
   }
 }
 
+// The list forms (lfa_k_iov.hpp): one kernel family per (op, element type)
+// on top of the sharing above.  ATOMIC_WRITE only moves bytes, so it runs the
+// unsigned integer of the element's width whatever the datatype.
+template <int OP, typename F>
+static int by_iov_type(int dt, F &&f) {
+  if constexpr (OP == OP_WRITE) {
+    switch (lfa_reduce_datatype_size((lfa_datatype)dt)) {
+      case 1: return f((uint8_t *)0);
+      case 2: return f((uint16_t *)0);
+      case 4: return f((uint32_t *)0);
+      case 8: return f((uint64_t *)0);
+      case 16: return f((u128 *)0);
+      default: return -LFA_EOPNOTSUPP;
+    }
+  } else {
+    return by_reduce_type<OP>(dt, f);
+  }
+}
+
 }  // namespace lfa
 
 #ifndef LFA_OP
@@ -119,7 +140,25 @@ extern "C" int LFA_CAT(lfa__write_op, LFA_OP)(int dt, void *dst,
 }
 #endif
 
+#if LFA_OP != 10
+extern "C" int LFA_CAT(lfa__writev_op, LFA_OP)(int dt, const lfa_iov_args *a,
+                                               unsigned ntile, void *stream) {
+  return lfa::by_iov_type<LFA_OP>(dt, [&](auto *tag) {
+    typedef typename std::remove_pointer<decltype(tag)>::type T;
+    return lfa::launch_writev<LFA_OP, T>(*a, ntile, (hipStream_t)stream);
+  });
+}
+#endif
+
 #if LFA_OP <= 9
+extern "C" int LFA_CAT(lfa__treev_op, LFA_OP)(int dt, const lfa_iov_args *a, int nsrc,
+                                              unsigned ntile, void *stream) {
+  return lfa::by_reduce_type<LFA_OP>(dt, [&](auto *tag) {
+    typedef typename std::remove_pointer<decltype(tag)>::type T;
+    return lfa::launch_treev<LFA_OP, T>(*a, nsrc, ntile, (hipStream_t)stream);
+  });
+}
+
 extern "C" int LFA_CAT(lfa__tree_op, LFA_OP)(int dt, void *dst,
                                              const void *const *srcs, int nsrc,
                                              size_t cnt, void *stream) {

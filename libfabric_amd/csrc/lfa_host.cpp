@@ -20,6 +20,9 @@
 #include <string.h>
 
 #include <type_traits>
+#include <algorithm>
+#include <utility>
+#include <vector>
 
 #include "lfa_ops.hpp"
 #include "../../include/lfa_atomic.h"
@@ -253,6 +256,48 @@ int lfa_host_reduce_tree(enum lfa_op op, enum lfa_datatype dt, void *dst,
       return lfa::host_tree<OP, T>(dst, srcs, nsrc, cnt);
     });
   });
+}
+
+// The list forms' argument check, shared by lfa_host_writev and the device
+// forms of lfa_capi.cpp: everything that makes a call -LFA_EINVAL, found
+// before any element is touched.  `src` may be null (lfa_reduce_treev_async
+// has no src list).  Two dst segments must not share a byte: separate calls
+// would order them, one launch cannot.  The ranges are sorted by start
+// (O(nseg log nseg)) and each start is compared with the end of the range
+// before it; the scan stops at the first overlap, so up to there that end is
+// also the furthest end seen.  Only dst ranges are compared: an input that
+// overlaps another segment's dst is the caller's to avoid (lfa_atomic.h).
+int lfa__iov_check(const struct lfa_ioc *dst, const struct lfa_ioc *src, int has_src,
+                   size_t nseg, size_t esz) {
+  if (nseg > LFA_IOV_MAX || !dst || (has_src && !src) || !esz) return -LFA_EINVAL;
+  static thread_local std::vector<std::pair<uintptr_t, uintptr_t>> range;
+  range.clear();
+  for (size_t i = 0; i < nseg; i++) {
+    const size_t n = dst[i].count;
+    if (has_src && src[i].count != n) return -LFA_EINVAL;
+    if (!n) continue;
+    if (!dst[i].addr || (has_src && !src[i].addr)) return -LFA_EINVAL;
+    const uintptr_t lo = (uintptr_t)dst[i].addr;
+    if (n > SIZE_MAX / esz || lo + n * esz < lo) return -LFA_EINVAL;
+    range.emplace_back(lo, lo + n * esz);
+  }
+  std::sort(range.begin(), range.end());
+  uintptr_t end = 0;
+  for (const auto &r : range) {
+    if (r.first < end) return -LFA_EINVAL;
+    end = r.second;
+  }
+  return 0;
+}
+
+int lfa_host_writev(enum lfa_op op, enum lfa_datatype dt, const struct lfa_ioc *dst,
+                    const struct lfa_ioc *src, size_t nseg) {
+  if (lfa_reduce_valid(dt, op)) return -LFA_EOPNOTSUPP;
+  if (!nseg) return 0;
+  int rc = lfa__iov_check(dst, src, 1, nseg, lfa_reduce_datatype_size(dt));
+  for (size_t i = 0; i < nseg && !rc; i++)
+    rc = lfa_host_write(op, dt, dst[i].addr, src[i].addr, dst[i].count);
+  return rc;
 }
 
 }  // extern "C"

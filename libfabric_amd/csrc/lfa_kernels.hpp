@@ -387,3 +387,4 @@ __global__ __launch_bounds__(kBlock) void combine_unaligned(
 #include "lfa_k_oneshot.hpp"
 #include "lfa_k_fetch.hpp"
 #include "lfa_k_launch.hpp"
+#include "lfa_k_iov.hpp"
