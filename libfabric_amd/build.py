@@ -53,8 +53,11 @@ def build_lfa(jobs: int = 8, verbose: bool = False) -> str:
     kern = os.path.join(CSRC, "lfa_combine.hip")
     hdrs = [os.path.join(CSRC, "lfa_ops.hpp"), os.path.join(CSRC, "lfa_kernels.hpp"),
             os.path.join(CSRC, "lfa_k_iov.hpp"), os.path.join(CSRC, "lfa_iov.h"),
+            os.path.join(CSRC, "lfa_split.h"),
             *(os.path.join(CSRC, f"lfa_k_{p}.hpp") for p in ("tree", "oneshot", "fetch", "launch")),
             os.path.join(INC, "lfa_atomic.h"), os.path.join(INC, "lfa_fabric.h")]
+    # forms only the tuning objects include: editing one rebuilds no product object
+    tune_hdrs = hdrs + [os.path.join(CSRC, "lfa_tune_forms.hpp")]
     steps = []
     objs = []
     for op in WRITE_OPS:
@@ -68,7 +71,7 @@ def build_lfa(jobs: int = 8, verbose: bool = False) -> str:
         tune = os.path.join(CSRC, name + ".hip")
         tune_o = os.path.join(BUILD, name + ".o")
         tune_objs.append(tune_o)
-        if _newer(tune_o, [tune] + hdrs):
+        if _newer(tune_o, [tune] + tune_hdrs):
             steps.append([HIPCC, *HIP_FLAGS, "-c", tune, "-o", tune_o])
     # the tree_put register-pressure probe (tools/probe_treeput_narrow.py)
     probe = os.path.join(CSRC, "lfa_probe.hip")

@@ -10,8 +10,8 @@
 //                  wave DMAs 4 KiB of each operand into LDS (global_load_lds,
 //                  nt), reads it back with ds_read_b128, applies OP and stores
 //                  nt; every wave-instruction moves 1 KiB of consecutive bytes.
-//   combine_vec    the register-staged form of the same (tuning reference,
-//                  built only into liblfa_tune.so).
+//                  One tile body, lds_tile, which combine_lds_taper (short
+//                  tiles for the last workgroups) and combine_iov share.
 //   combine_elem   the same op for misaligned heads/tails and for buffers that
 //                  are not co-aligned mod 16 (one element per lane, coalesced).
 //   reduce_tree_*  N inputs → 1 output in ONE pass, in prov/coll's
@@ -21,10 +21,15 @@
 //   reduce_tree_put the same tree with its result written to several
 //                  outputs, every access system scope: the LFA_ALGO_P2P kernel
 //                  that reads peers' HBM and pushes into it over xGMI.
-//   fetch_vec/elem the fetch (readwrite) and compare-swap tables
-//                  (util_atomic.c:924-980): res = old dst, then the update.
+//   fetch_lds/elem the fetch (readwrite) and compare-swap tables
+//                  (util_atomic.c:924-980): res = old dst, then the update;
+//                  fetch_lds and fetch_lds_taper over one tile body, fetch_tile.
+//   combine_iov, reduce_iov  the list (fi_ioc) forms: every segment of a call
+//                  in one launch (lfa_k_iov.hpp).
 //
-// Kernels and launchers: lfa_kernels.hpp.  Semantics: lfa_ops.hpp.  Build: hipcc --offload-arch=gfx950 -O3
+// Kernels and launchers: lfa_kernels.hpp (how a buffer is cut into head,
+// vectors and tail: lfa_split.h).  The forms only the tuning library builds:
+// lfa_tune_forms.hpp, not included here.  Semantics: lfa_ops.hpp.  Build: hipcc --offload-arch=gfx950 -O3
 // -ffp-contract=off -DLFA_OP=<op>, once per enum fi_op row (0..18; see
 // libfabric_amd/build.py).
 #include "lfa_kernels.hpp"

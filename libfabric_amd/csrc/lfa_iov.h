@@ -24,6 +24,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "lfa_split.h"
+
 #define LFA_IOV_TILE 16384u /* bytes of dst per workgroup: 4 KiB per wave */
 #define LFA_IOV_INLINE 64   /* words: 512 bytes of kernel arguments */
 #define LFA_IOV_TREE_LEAVES 8 /* the fused tree form's widest kernel: 2..15 inputs */
@@ -37,11 +39,7 @@ struct lfa_iov_args {
   uint64_t inl[LFA_IOV_INLINE];
 };
 
-#ifdef __HIPCC__
-#define LFA_IOV_FN __host__ __device__ static inline
-#else
-#define LFA_IOV_FN static inline
-#endif
+#define LFA_IOV_FN LFA_SPLIT_FN
 
 LFA_IOV_FN size_t lfa_iov_prefix_words(size_t nseg) { return (nseg + 2) / 2; }
 
@@ -49,15 +47,10 @@ LFA_IOV_FN size_t lfa_iov_prefix_words(size_t nseg) { return (nseg + 2) / 2; }
  * whose operands' addresses OR to `any`.
  * Operands not aligned to the element: tiles of LFA_IOV_TILE / esz elements
  * from element 0.  Otherwise the elements before dst's first 16-byte boundary
- * (the head) belong to tile 0 and the tiles start at that boundary, so every
+ * (the head, lfa_split_head) belong to tile 0 and the tiles start at that boundary, so every
  * tile boundary inside a segment is a 16-byte boundary of dst. */
-LFA_IOV_FN size_t lfa_iov_head(uintptr_t dst, size_t count, size_t esz) {
-  size_t head = ((16 - dst % 16) % 16) / esz;
-  return head < count ? head : count;
-}
-
 LFA_IOV_FN size_t lfa_iov_tiles(uintptr_t dst, uintptr_t any, size_t count, size_t esz) {
-  const size_t rest = any % esz ? count : count - lfa_iov_head(dst, count, esz);
+  const size_t rest = any % esz ? count : count - lfa_split_head(dst, count, esz);
   const size_t n = (rest * esz + LFA_IOV_TILE - 1) / LFA_IOV_TILE;
   return n ? n : 1;
 }

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(kLdsWaves * 64) void combine_iov(IovArgs a) {
   // Element work of this tile: [0, n0) and [off1, off1 + n1), one call site.
   // Tile 0 always owns the head, the elements before dst's first 16-byte
   // boundary.
-  const size_t head = lfa_iov_head(pd, cnt, E), n0 = tile == 0 ? head : 0;
+  const size_t head = lfa_split_head(pd, cnt, E), n0 = tile == 0 ? head : 0;
   size_t off1, n1;
   if ((pd ^ ps) % 16 == 0) {
     const size_t nvec = (cnt - head) * E / 16;
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(kBlock) void reduce_iov(IovTreeArgs ta) {
   // Element work of this tile: [0, n0) and [off1, off1 + n1), one call site;
   // `bytes`: some operand is not aligned to the element and all move byte-wise.
   const bool bytes = any % E != 0;
-  const size_t head = bytes ? 0 : lfa_iov_head(pd, cnt, E), n0 = tile == 0 ? head : 0;
+  const size_t head = bytes ? 0 : lfa_split_head(pd, cnt, E), n0 = tile == 0 ? head : 0;
   size_t off1, n1;
   if (!bytes && mis % 16 == 0) {
     const size_t nvec = (cnt - head) * E / 16, hb = head * E;
@@ -182,7 +182,7 @@ static int launch_writev(const IovArgs &a, unsigned ntile, hipStream_t s) {
     return -LFA_EOPNOTSUPP;
   } else {
     hipLaunchKernelGGL((combine_iov<OP, T>), dim3(ntile), dim3(kBlock), 0, s, a);
-    return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO;
+    return launch_rc();
   }
 }
 
@@ -206,7 +206,7 @@ static int launch_treev(const IovArgs &a, int nsrc, unsigned ntile, hipStream_t 
       case 8: hipLaunchKernelGGL((reduce_iov<OP, T, 8>), grid, block, 0, s, ta); break;
       default: return -LFA_EINVAL;
     }
-    return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO;
+    return launch_rc();
   }
 }
 

@@ -24,6 +24,13 @@ static inline unsigned grid_for(size_t work, size_t per_block, unsigned cap) {
 }
 constexpr unsigned kElemGridCap = 256 * 8;  // 8 workgroups per CU, grid-stride
 
+// What every launcher returns once its kernels are enqueued.
+static inline int launch_rc() { return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO; }
+
+// Every launcher below cuts its buffer the same way (lfa_split.h): the byte
+// path gets its own kernel; otherwise the vector body runs over sp.nvec
+// vectors from element sp.head, and ONE element launch covers the head and
+// the tail — or, off the vector path, the whole buffer (sp.head == cnt).
 template <int OP, typename T>
 static int launch_write(void *dst, const void *src, size_t cnt,
                         hipStream_t s, bool mapped = false) {
@@ -31,58 +38,47 @@ static int launch_write(void *dst, const void *src, size_t cnt,
     return -LFA_EOPNOTSUPP;
   } else {
     constexpr size_t E = sizeof(T);
-    uintptr_t pd = (uintptr_t)dst, ps = (uintptr_t)src;
     if (cnt == 0) return 0;
-    if (pd % E || ps % E) {
+    const lfa_path path = lfa_split_path(&dst, 1, &src, 1, E);
+    if (path == LFA_PATH_BYTES) {
       hipLaunchKernelGGL((combine_unaligned<OP, T>),
                          dim3(grid_for(cnt, kBlock, kElemGridCap)), dim3(kBlock),
                          0, s, (unsigned char *)dst, (const unsigned char *)src,
                          cnt);
-    } else if ((pd ^ ps) % 16 == 0 && E <= 16) {
-      size_t head = ((16 - pd % 16) % 16) / E;
-      if (head > cnt) head = cnt;
-      size_t nvec = (cnt - head) * E / 16;
-      size_t body = nvec * 16 / E;
-      size_t tail = cnt - head - body;
-      if (nvec) {
-        u32x4 *d = (u32x4 *)((char *)dst + head * E);
-        const u32x4 *v = (const u32x4 *)((const char *)src + head * E);
-        const dim3 grid(grid_for(nvec, (size_t)kLdsWaves * 64 * kUnroll, 0x7fffffffu));
-        if (mapped) {
-          // host-mapped operands (lfa_atomic_write_staged's zero-copy form):
-          // PCIe-bound, so the tiling does not matter; the plain write-through
-          // body at every size keeps these ~10 ms launches out of the device
-          // kernels' instantiations in traces (rocprofv3 stats per kernel)
-          hipLaunchKernelGGL((combine_lds<OP, T, kUnroll, kStoreSc1>), grid,
-                             dim3(kLdsWaves * 64), 0, s, d, v, nvec);
-        } else if (nvec * 16 >= kTaperBytes && nvec * 16 < kSc1Bytes) {
-          // the last 1/kTaperDiv of the vectors in 1-KiB tiles
-          const size_t hv = (size_t)kLdsWaves * 64 * kUnroll;
-          size_t split = nvec - nvec / kTaperDiv;
-          split -= split % hv;
-          const unsigned head = (unsigned)(split / hv);
-          const unsigned tail = (unsigned)((nvec - split + kLdsWaves * 64 - 1) / (kLdsWaves * 64));
-          hipLaunchKernelGGL((combine_lds_taper<OP, T, kUnroll, kStoreSc1>), dim3(head + tail),
-                             dim3(kLdsWaves * 64), 0, s, d, v, nvec, split, head);
-        } else if (nvec * 16 < kSc1Bytes)
-          hipLaunchKernelGGL((combine_lds<OP, T, kUnroll, kStoreSc1>), grid,
-                             dim3(kLdsWaves * 64), 0, s, d, v, nvec);
-        else
-          hipLaunchKernelGGL((combine_lds<OP, T, kUnroll, kStoreNt>), grid,
-                             dim3(kLdsWaves * 64), 0, s, d, v, nvec);
-      }
-      if (head + tail)
-        hipLaunchKernelGGL((combine_elem<OP, T>),
-                           dim3(grid_for(head + tail, kBlock, kElemGridCap)),
-                           dim3(kBlock), 0, s, (T *)dst, (const T *)src, head,
-                           head + body, tail);
-    } else {
-      hipLaunchKernelGGL((combine_elem<OP, T>),
-                         dim3(grid_for(cnt, kBlock, kElemGridCap)), dim3(kBlock),
-                         0, s, (T *)dst, (const T *)src, cnt, (size_t)0,
-                         (size_t)0);
+      return launch_rc();
     }
-    return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO;
+    const lfa_split sp = lfa_split_of(path, (uintptr_t)dst, cnt, E);
+    if (const size_t nvec = sp.nvec) {
+      u32x4 *d = (u32x4 *)((char *)dst + sp.head * E);
+      const u32x4 *v = (const u32x4 *)((const char *)src + sp.head * E);
+      constexpr size_t hv = (size_t)kLdsWaves * 64 * kUnroll;
+      const dim3 grid(grid_for(nvec, hv, 0x7fffffffu));
+      if (mapped) {
+        // host-mapped operands (lfa_atomic_write_staged's zero-copy form):
+        // PCIe-bound, so the tiling does not matter; the plain write-through
+        // body at every size keeps these ~10 ms launches out of the device
+        // kernels' instantiations in traces (rocprofv3 stats per kernel)
+        hipLaunchKernelGGL((combine_lds<OP, T, kUnroll, kStoreSc1>), grid,
+                           dim3(kLdsWaves * 64), 0, s, d, v, nvec);
+      } else if (nvec * 16 >= kTaperBytes && nvec * 16 < kSc1Bytes) {
+        // the last 1/kTaperDiv of the vectors in 1-KiB tiles
+        const lfa_taper tp = lfa_split_taper(nvec, kTaperDiv, hv, kLdsWaves * 64);
+        hipLaunchKernelGGL((combine_lds_taper<OP, T, kUnroll, kStoreSc1>),
+                           dim3(tp.nhead + tp.ntail), dim3(kLdsWaves * 64), 0, s, d, v, nvec,
+                           tp.split, tp.nhead);
+      } else if (nvec * 16 < kSc1Bytes)
+        hipLaunchKernelGGL((combine_lds<OP, T, kUnroll, kStoreSc1>), grid,
+                           dim3(kLdsWaves * 64), 0, s, d, v, nvec);
+      else
+        hipLaunchKernelGGL((combine_lds<OP, T, kUnroll, kStoreNt>), grid,
+                           dim3(kLdsWaves * 64), 0, s, d, v, nvec);
+    }
+    if (sp.head + sp.tail)
+      hipLaunchKernelGGL((combine_elem<OP, T>),
+                         dim3(grid_for(sp.head + sp.tail, kBlock, kElemGridCap)),
+                         dim3(kBlock), 0, s, (T *)dst, (const T *)src, sp.head,
+                         sp.head + sp.body, sp.tail);
+    return launch_rc();
   }
 }
 
@@ -99,7 +95,7 @@ static void launch_tree_lds(const TreeArgs &b, int nsrc, u32x4 *dst,
 
 constexpr unsigned kTreeCapLds = 41u << 10;
 
-template <int OP, typename T, int NLEAF, bool ALL = false>
+template <int OP, typename T, int NLEAF>
 static void launch_tree_body(const TreeArgs &b, int nsrc, u32x4 *dst,
                              size_t nvec, hipStream_t s, int variant = -1) {
   // Product choice (bench.py --tune-tree, profiles/r01_tune_tree_sc1.log):
@@ -127,11 +123,12 @@ static void launch_tree_body(const TreeArgs &b, int nsrc, u32x4 *dst,
   if (variant < 0 && nvec * 16 < kSc1Bytes) variant = 11;
   if (variant < 0) variant = nsrc <= 2 ? 3 : nsrc > 8 ? 2 : 1;
   // nsrc lies in [NLEAF, 2·NLEAF): only these forms are reachable from the
-  // product choice, so only they are instantiated into liblfa.so (ALL: the
-  // tuning library, which times every form at every fan-in)
-  constexpr bool has3 = ALL || NLEAF == 2;   // nsrc <= 2
-  constexpr bool has2 = ALL || NLEAF >= 8;   // nsrc > 8
-  constexpr bool has1 = ALL || NLEAF <= 8;   // 3 <= nsrc <= 8
+  // product choice, so only they are instantiated into liblfa.so (the
+  // tuning library times every form at every fan-in: launch_tree_tune_form,
+  // lfa_tune_forms.hpp)
+  constexpr bool has3 = NLEAF == 2;   // nsrc <= 2
+  constexpr bool has2 = NLEAF >= 8;   // nsrc > 8
+  constexpr bool has1 = NLEAF <= 8;   // 3 <= nsrc <= 8
   if (variant == 2) {
     if constexpr (has2) {
       hipLaunchKernelGGL((reduce_tree_chunk<OP, T, NLEAF, 2>),
@@ -151,41 +148,11 @@ static void launch_tree_body(const TreeArgs &b, int nsrc, u32x4 *dst,
                          dim3(kBlock), 0, s, b, dst, nvec);
       return;
     }
-  } else if (variant >= 20 && variant <= 24) {
-    if constexpr (ALL) {
-      // round 5: the write-through chunk form at capped occupancy (dynamic
-      // LDS the body never touches) and at 4 vectors per lane
-      constexpr unsigned kCap[5] = {41u << 10, 54u << 10, 81u << 10, 0u, 54u << 10};
-      const unsigned lds = kCap[variant - 20];
-      if (variant < 23)
-        hipLaunchKernelGGL((reduce_tree_chunk<OP, T, NLEAF, 2, kStoreSc1>),
-                           dim3(grid_for(nvec, (size_t)kBlock * 2, 0x7fffffffu)),
-                           dim3(kBlock), lds, s, b, dst, nvec);
-      else
-        hipLaunchKernelGGL((reduce_tree_chunk<OP, T, NLEAF, 4, kStoreSc1>),
-                           dim3(grid_for(nvec, (size_t)kBlock * 4, 0x7fffffffu)),
-                           dim3(kBlock), lds, s, b, dst, nvec);
-      return;
-    }
-  } else if (variant == 27 || variant == 28) {
-    if constexpr (ALL) {
-      // round 5: the push kernel's body with one output at 2 KiB per wave per
-      // input; 28 at <= 3 workgroups per CU
-      PutArgs pa;
-      pa.t = b;
-      memset(pa.out, 0, sizeof(pa.out));
-      pa.out[0] = dst;
-      pa.nout = 1;
-      hipLaunchKernelGGL((reduce_tree_put<OP, T, NLEAF, 2>),
-                         dim3(grid_for(nvec, (size_t)kBlock * 2, 0x7fffffffu)), dim3(kBlock),
-                         variant == 28 ? (41u << 10) : 0u, s, pa, nvec);
-      return;
-    }
-  } else if (variant == 25 || variant == 26) {
-    if constexpr (ALL || kPutBody) {
+  } else if (variant == 25) {
+    if constexpr (kPutBody) {
       // round 5: the P2P push kernel's body with one output (4 KiB per wave
       // per input through tile-sized buffer descriptors, system-scope nt
-      // loads, write-through stores); 26 at <= 3 workgroups per CU
+      // loads, write-through stores)
       PutArgs pa;
       pa.t = b;
       memset(pa.out, 0, sizeof(pa.out));
@@ -193,18 +160,7 @@ static void launch_tree_body(const TreeArgs &b, int nsrc, u32x4 *dst,
       pa.nout = 1;
       hipLaunchKernelGGL((reduce_tree_put<OP, T, NLEAF, 4>),
                          dim3(grid_for(nvec, (size_t)kBlock * 4, 0x7fffffffu)), dim3(kBlock),
-                         variant == 26 ? (41u << 10) : 0u, s, pa, nvec);
-      return;
-    }
-  } else if (variant == 12) {
-    if constexpr (ALL) {
-      // the last 1/8 of the vectors one per lane (reduce_tree_taper)
-      size_t split = nvec - nvec / 8;
-      split -= split % ((size_t)kBlock * 2);
-      const unsigned head = (unsigned)(split / ((size_t)kBlock * 2));
-      const unsigned tail = (unsigned)((nvec - split + kBlock - 1) / kBlock);
-      hipLaunchKernelGGL((reduce_tree_taper<OP, T, NLEAF>), dim3(head + tail), dim3(kBlock), 0,
-                         s, b, dst, nvec, split, head);
+                         0, s, pa, nvec);
       return;
     }
   }
@@ -247,25 +203,21 @@ struct ProductTreeBody {
 };
 
 template <int OP, typename T, int NLEAF, typename Body = ProductTreeBody>
-static int launch_tree_n(const TreeArgs &a, int nsrc, void *dst, size_t cnt,
-                         bool vec, size_t head, size_t nvec, hipStream_t s,
-                         int variant) {
+static int launch_tree_n(const TreeArgs &a, int nsrc, void *dst, const lfa_split &sp,
+                         hipStream_t s, int variant) {
   constexpr size_t E = sizeof(T);
-  if (vec && nvec) {
+  if (sp.nvec) {
     TreeArgs b = a;
     for (int k = 0; k < kMaxLeaf; k++)
-      if (b.in[k]) b.in[k] = (const char *)b.in[k] + head * E;
-    Body::template launch<OP, T, NLEAF>(b, nsrc, (u32x4 *)((char *)dst + head * E),
-                                        nvec, s, variant);
+      if (b.in[k]) b.in[k] = (const char *)b.in[k] + sp.head * E;
+    Body::template launch<OP, T, NLEAF>(b, nsrc, (u32x4 *)((char *)dst + sp.head * E),
+                                        sp.nvec, s, variant);
   }
-  size_t body = vec ? nvec * 16 / E : 0;
-  size_t n0 = vec ? head : cnt;
-  size_t tail = vec ? cnt - head - body : 0;
-  if (n0 + tail)
+  if (sp.head + sp.tail)
     hipLaunchKernelGGL((reduce_tree_elem<OP, T, NLEAF>),
-                       dim3(grid_for(n0 + tail, kBlock, kElemGridCap)),
-                       dim3(kBlock), 0, s, a, (T *)dst, n0, head + body, tail);
-  return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO;
+                       dim3(grid_for(sp.head + sp.tail, kBlock, kElemGridCap)),
+                       dim3(kBlock), 0, s, a, (T *)dst, sp.head, sp.head + sp.body, sp.tail);
+  return launch_rc();
 }
 
 template <int OP, typename T, typename Body = ProductTreeBody>
@@ -284,27 +236,24 @@ static int launch_tree(void *dst, const void *const *srcs, int nsrc,
     }
     TreeArgs a;
     const int pof2 = tree_leaves(a, srcs, nsrc);
-    uintptr_t mis = (uintptr_t)dst % 16, anyelem = (uintptr_t)dst % E;
-    for (int k = 0; k < nsrc; k++) {
-      mis |= ((uintptr_t)srcs[k] % 16) ^ ((uintptr_t)dst % 16);
-      anyelem |= (uintptr_t)srcs[k] % E;
-    }
-    if (anyelem) {
+    lfa_path path = lfa_split_path(&dst, 1, srcs, nsrc, E);
+    if (path == LFA_PATH_BYTES) {
       hipLaunchKernelGGL((reduce_tree_unaligned<OP, T>),
                          dim3(grid_for(cnt, kBlock, kElemGridCap)), dim3(kBlock), 0, s,
                          a, pof2, dst, cnt);
-      return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO;
+      return launch_rc();
     }
-    bool vec = (mis == 0) && E <= 16;
-    size_t head = vec ? ((16 - (uintptr_t)dst % 16) % 16) / E : 0;
-    if (head > cnt) head = cnt;
-    size_t nvec = vec ? (cnt - head) * E / 16 : 0;
+    // The tree's vector body has only ever run from a 16-byte aligned dst:
+    // operands co-aligned off the boundary take the element path here, where
+    // the other launchers peel a head.
+    if ((uintptr_t)dst % 16) path = LFA_PATH_ELEM;
+    const lfa_split sp = lfa_split_of(path, (uintptr_t)dst, cnt, E);
     switch (pof2) {
-      case 2: return launch_tree_n<OP, T, 2, Body>(a, nsrc, dst, cnt, vec, head, nvec, s, variant);
-      case 4: return launch_tree_n<OP, T, 4, Body>(a, nsrc, dst, cnt, vec, head, nvec, s, variant);
-      case 8: return launch_tree_n<OP, T, 8, Body>(a, nsrc, dst, cnt, vec, head, nvec, s, variant);
-      case 16: return launch_tree_n<OP, T, 16, Body>(a, nsrc, dst, cnt, vec, head, nvec, s, variant);
-      case 32: return launch_tree_n<OP, T, 32, Body>(a, nsrc, dst, cnt, vec, head, nvec, s, variant);
+      case 2: return launch_tree_n<OP, T, 2, Body>(a, nsrc, dst, sp, s, variant);
+      case 4: return launch_tree_n<OP, T, 4, Body>(a, nsrc, dst, sp, s, variant);
+      case 8: return launch_tree_n<OP, T, 8, Body>(a, nsrc, dst, sp, s, variant);
+      case 16: return launch_tree_n<OP, T, 16, Body>(a, nsrc, dst, sp, s, variant);
+      case 32: return launch_tree_n<OP, T, 32, Body>(a, nsrc, dst, sp, s, variant);
       default: return -LFA_EINVAL;
     }
   }
@@ -326,8 +275,7 @@ constexpr int kPutNarrowOuts = 6;
 constexpr unsigned kPutNarrowLds = 96u << 10;
 
 template <int OP, typename T, int NLEAF, int UF = 0>
-static int launch_tree_put_n(const PutArgs &a, size_t cnt, bool vec, size_t head,
-                             hipStream_t s) {
+static int launch_tree_put_n(const PutArgs &a, const lfa_split &sp, hipStream_t s) {
   constexpr size_t E = sizeof(T);
   // 4 KiB of every input per wave (tune variant 14: +2 points over 2 KiB at
   // 8 inputs) where the registers allow it: up to 8 leaves of 4-16 B
@@ -335,12 +283,11 @@ static int launch_tree_put_n(const PutArgs &a, size_t cnt, bool vec, size_t head
   // needs > 256 VGPRs and gave wrong uint8 results at 16 leaves).
   constexpr int U = UF ? UF : (NLEAF <= 8 && E >= 4) ? 4 : 2;
   constexpr bool kNarrowable = UF == 0 && NLEAF <= 8 && E >= 4;
-  size_t nvec = vec ? (cnt - head) * E / 16 : 0;
-  if (nvec) {
+  if (const size_t nvec = sp.nvec) {
     PutArgs b = a;
     for (int k = 0; k < kMaxLeaf; k++)
-      if (b.t.in[k]) b.t.in[k] = (const char *)b.t.in[k] + head * E;
-    for (int j = 0; j < b.nout; j++) b.out[j] = (char *)b.out[j] + head * E;
+      if (b.t.in[k]) b.t.in[k] = (const char *)b.t.in[k] + sp.head * E;
+    for (int j = 0; j < b.nout; j++) b.out[j] = (char *)b.out[j] + sp.head * E;
     if (kNarrowable && b.nout >= kPutNarrowOuts)
       hipLaunchKernelGGL((reduce_tree_put<OP, T, NLEAF, 2>),
                          dim3(grid_for(nvec, (size_t)kBlock * 2, 0x7fffffffu)),
@@ -350,14 +297,11 @@ static int launch_tree_put_n(const PutArgs &a, size_t cnt, bool vec, size_t head
                          dim3(grid_for(nvec, (size_t)kBlock * U, 0x7fffffffu)),
                          dim3(kBlock), 0, s, b, nvec);
   }
-  size_t body = nvec * 16 / E;
-  size_t n0 = vec ? head : cnt;
-  size_t tail = vec ? cnt - head - body : 0;
-  if (n0 + tail)
+  if (sp.head + sp.tail)
     hipLaunchKernelGGL((reduce_tree_put_elem<OP, T, NLEAF>),
-                       dim3(grid_for(n0 + tail, kBlock, kElemGridCap)), dim3(kBlock),
-                       0, s, a, n0, head + body, tail);
-  return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO;
+                       dim3(grid_for(sp.head + sp.tail, kBlock, kElemGridCap)), dim3(kBlock),
+                       0, s, a, sp.head, sp.head + sp.body, sp.tail);
+  return launch_rc();
 }
 
 // UF != 0 forces the vector body's tile (KiB per wave) — liblfa_tune.so only.
@@ -374,18 +318,9 @@ static int launch_tree_put(void *const *dsts, int ndst, const void *const *srcs,
     const int pof2 = tree_leaves(a.t, srcs, nsrc);
     memset(a.out, 0, sizeof(a.out));
     a.nout = ndst;
-    const uintptr_t p0 = (uintptr_t)dsts[0];
-    uintptr_t mis = 0, anyelem = 0;
-    for (int k = 0; k < nsrc; k++) {
-      mis |= ((uintptr_t)srcs[k] ^ p0) % 16;
-      anyelem |= (uintptr_t)srcs[k] % E;
-    }
-    for (int j = 0; j < ndst; j++) {
-      a.out[j] = dsts[j];
-      mis |= ((uintptr_t)dsts[j] ^ p0) % 16;
-      anyelem |= (uintptr_t)dsts[j] % E;
-    }
-    if (anyelem) {
+    for (int j = 0; j < ndst; j++) a.out[j] = dsts[j];
+    const lfa_path path = lfa_split_path(dsts, ndst, srcs, nsrc, E);
+    if (path == LFA_PATH_BYTES) {
       uint32_t in_sys = 0, out_sys = 0;
       for (int k = 0; k < nsrc; k++)
         if ((uintptr_t)srcs[k] % E == 0) in_sys |= 1u << k;
@@ -394,18 +329,16 @@ static int launch_tree_put(void *const *dsts, int ndst, const void *const *srcs,
       hipLaunchKernelGGL((reduce_tree_put_unaligned<OP, T>),
                          dim3(grid_for(cnt, kBlock, kElemGridCap)), dim3(kBlock), 0, s,
                          a, pof2, in_sys, out_sys, cnt);
-      return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO;
+      return launch_rc();
     }
-    const bool vec = mis == 0 && E <= 16;
-    size_t head = vec ? ((16 - p0 % 16) % 16) / E : 0;
-    if (head > cnt) head = cnt;
+    const lfa_split sp = lfa_split_of(path, (uintptr_t)dsts[0], cnt, E);
     switch (pof2) {
-      case 1: return launch_tree_put_n<OP, T, 1, UF>(a, cnt, vec, head, s);
-      case 2: return launch_tree_put_n<OP, T, 2, UF>(a, cnt, vec, head, s);
-      case 4: return launch_tree_put_n<OP, T, 4, UF>(a, cnt, vec, head, s);
-      case 8: return launch_tree_put_n<OP, T, 8, UF>(a, cnt, vec, head, s);
-      case 16: return launch_tree_put_n<OP, T, 16, UF>(a, cnt, vec, head, s);
-      case 32: return launch_tree_put_n<OP, T, 32, UF>(a, cnt, vec, head, s);
+      case 1: return launch_tree_put_n<OP, T, 1, UF>(a, sp, s);
+      case 2: return launch_tree_put_n<OP, T, 2, UF>(a, sp, s);
+      case 4: return launch_tree_put_n<OP, T, 4, UF>(a, sp, s);
+      case 8: return launch_tree_put_n<OP, T, 8, UF>(a, sp, s);
+      case 16: return launch_tree_put_n<OP, T, 16, UF>(a, sp, s);
+      case 32: return launch_tree_put_n<OP, T, 32, UF>(a, sp, s);
       default: return -LFA_EINVAL;
     }
   }
@@ -539,7 +472,7 @@ static int launch_oneshot(const lfa_oneshot &h, hipStream_t s) {
         default:
           return -LFA_EINVAL;
       }
-      return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO;
+      return launch_rc();
     }
     a.wait = n > 1 ? (const uint32_t *)(h.sym[r] + h.flag_off + LFA_SIG_OS_OFF) : nullptr;
     a.done_ctr = h.done_ctr;
@@ -576,7 +509,7 @@ static int launch_oneshot(const lfa_oneshot &h, hipStream_t s) {
       default:
         return -LFA_EINVAL;
     }
-    return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO;
+    return launch_rc();
   }
 }
 
@@ -587,22 +520,18 @@ static int launch_fetch(const void *const *ptrs, int nptr, size_t cnt,
                         hipStream_t s, MakeF &&make) {
   constexpr size_t E = sizeof(T);
   if (cnt == 0) return 0;
-  uintptr_t p0 = (uintptr_t)ptrs[0], mis = 0, elem_mis = 0;
-  for (int k = 0; k < nptr; k++) {
-    mis |= ((uintptr_t)ptrs[k] ^ p0) % 16;
-    elem_mis |= (uintptr_t)ptrs[k] % E;
-  }
-  if (elem_mis) {
+  const lfa_path path = lfa_split_path(ptrs, nptr, nullptr, 0, E);
+  if (path == LFA_PATH_BYTES) {
     auto f = make(std::integral_constant<bool, false>(), (size_t)0);
     hipLaunchKernelGGL(fetch_elem<decltype(f)>, dim3(grid_for(cnt, kBlock, kElemGridCap)),
                        dim3(kBlock), 0, s, f, cnt, (size_t)0, (size_t)0);
-  } else if (mis == 0 && E <= 16) {
-    size_t head = ((16 - p0 % 16) % 16) / E;
-    if (head > cnt) head = cnt;
-    size_t nvec = (cnt - head) * E / 16, body = nvec * 16 / E;
-    size_t tail = cnt - head - body;
-    auto f = make(std::integral_constant<bool, true>(), head);
-    using FF = decltype(f);
+    return launch_rc();
+  }
+  const lfa_split sp = lfa_split_of(path, (uintptr_t)ptrs[0], cnt, E);
+  // the functor's vector pointers start after the head (none off the vector path)
+  auto f = make(std::integral_constant<bool, true>(), path == LFA_PATH_VEC ? sp.head : (size_t)0);
+  using FF = decltype(f);
+  if (const size_t nvec = sp.nvec) {
     // 4 KiB per input per wave and write-through (sc1) stores at every size:
     // at 256 MiB per operand 168.0 us (79.9 %) for a float SUM readwrite and
     // 199.9 us (83.9 %) for a float CSWAP, against 174.3 / 204.8 us for the
@@ -610,7 +539,7 @@ static int launch_fetch(const void *const *ptrs, int nptr, size_t cnt,
     // (tools/probe_fetch.py --tune, profiles/r02_tune_fetch.log).  Two
     // output streams make write-through win even where combine_lds (one
     // output) keeps nt.  Round 3: two-input bodies (readwrite) store step by
-    // step as their loads land (fetch_drain), and from kSc1Bytes per operand
+    // step as their loads land (fetch_tile's DRAIN), and from kSc1Bytes per operand
     // with nt stores, as combine_lds does: 256 MiB float SUM 163.2 / 164.9 us
     // nt-drained vs 166.7 / 166.8 sc1-drained vs 172.2 sc1 (two boxes, back
     // to back, profiles/r03_tune_fetch*.log).  The three-input compare body
@@ -627,47 +556,35 @@ static int launch_fetch(const void *const *ptrs, int nptr, size_t cnt,
     // 167.0-167.3 -> 165.0-166.5 us, float CSWAP 215.6-215.9 -> 213.0-214.9 us,
     // three interleaved runs of 20 rounds on one box; UT 1 / 2 with the last
     // 1/16 .. 1/2 tapered measured within that (profiles/r06_tune_fetch_taper_*.jsonl).
-    constexpr int U = 4;
-    constexpr bool D = FF::kIn == 2;
-    const dim3 grid(grid_for(nvec, (size_t)kLdsWaves * 64 * U, 0x7fffffffu));
-    const bool nt = nvec * 16 >= kSc1Bytes;
-    if (nt) {
-      constexpr size_t hv = (size_t)kLdsWaves * 64 * U, tv = (size_t)kLdsWaves * 64;
-      size_t split = nvec - nvec / 4;
-      split -= split % hv;
-      const unsigned nhead = (unsigned)(split / hv);
-      const unsigned ntail = (unsigned)((nvec - split + tv - 1) / tv);
-      hipLaunchKernelGGL((fetch_lds_taper<U, 1, kStoreNt, FF>), dim3(nhead + ntail),
-                         dim3(kLdsWaves * 64), 0, s, f, nvec, split, nhead);
-    }
     // Below kSc1Bytes the two-input readwrite takes the same tail from
     // kFetchTaperBytes, on its write-through drained body (tune variant 21 vs
     // 6: 64 MiB 39.1 / 38.6 -> 38.5 / 38.4 us, 128 MiB 83.0 -> 81.7 us); the
     // compare body keeps its undrained form there, which the tapered one
     // trailed at 64 MiB (48.5 vs 49.5-50.1 us) and tied at 128
     // (profiles/r06_tune_fetch_taper_sc1.jsonl).
+    constexpr int U = 4;
+    constexpr bool D = FF::kIn == 2;
     constexpr size_t kFetchTaperBytes = (size_t)64 << 20;
-    if (nvec && !nt && FF::kIn == 2 && nvec * 16 >= kFetchTaperBytes) {
-      constexpr size_t hv = (size_t)kLdsWaves * 64 * U, tv = (size_t)kLdsWaves * 64;
-      size_t split = nvec - nvec / 4;
-      split -= split % hv;
-      const unsigned nhead = (unsigned)(split / hv);
-      const unsigned ntail = (unsigned)((nvec - split + tv - 1) / tv);
-      hipLaunchKernelGGL((fetch_lds_taper<U, 1, kStoreSc1, FF>), dim3(nhead + ntail),
-                         dim3(kLdsWaves * 64), 0, s, f, nvec, split, nhead);
-    } else if (nvec && !nt)
-      hipLaunchKernelGGL((fetch_lds<U, kStoreSc1, FF, D>), grid, dim3(kLdsWaves * 64), 0, s,
-                         f, nvec);
-    if (head + tail)
-      hipLaunchKernelGGL(fetch_elem<decltype(f)>,
-                         dim3(grid_for(head + tail, kBlock, kElemGridCap)),
-                         dim3(kBlock), 0, s, f, head, head + body, tail);
-  } else {
-    auto f = make(std::integral_constant<bool, true>(), (size_t)0);
-    hipLaunchKernelGGL(fetch_elem<decltype(f)>, dim3(grid_for(cnt, kBlock, kElemGridCap)),
-                       dim3(kBlock), 0, s, f, cnt, (size_t)0, (size_t)0);
+    constexpr size_t hv = (size_t)kLdsWaves * 64 * U, tv = (size_t)kLdsWaves * 64;
+    const bool nt = nvec * 16 >= kSc1Bytes;
+    if (nt || (FF::kIn == 2 && nvec * 16 >= kFetchTaperBytes)) {
+      const lfa_taper tp = lfa_split_taper(nvec, 4, hv, tv);
+      const dim3 grid(tp.nhead + tp.ntail);
+      if (nt)
+        hipLaunchKernelGGL((fetch_lds_taper<U, 1, kStoreNt, FF>), grid, dim3(kLdsWaves * 64), 0,
+                           s, f, nvec, tp.split, tp.nhead);
+      else
+        hipLaunchKernelGGL((fetch_lds_taper<U, 1, kStoreSc1, FF>), grid, dim3(kLdsWaves * 64),
+                           0, s, f, nvec, tp.split, tp.nhead);
+    } else {
+      hipLaunchKernelGGL((fetch_lds<U, kStoreSc1, FF, D>), dim3(grid_for(nvec, hv, 0x7fffffffu)),
+                         dim3(kLdsWaves * 64), 0, s, f, nvec);
+    }
   }
-  return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO;
+  if (sp.head + sp.tail)
+    hipLaunchKernelGGL(fetch_elem<FF>, dim3(grid_for(sp.head + sp.tail, kBlock, kElemGridCap)),
+                       dim3(kBlock), 0, s, f, sp.head, sp.head + sp.body, sp.tail);
+  return launch_rc();
 }
 
 template <int OP, typename T>

@@ -64,17 +64,6 @@ __device__ __forceinline__ V tree_eval(const TreeArgs &a, size_t i) {
       a, [&](int k) { return ((const V *)a.in[k])[i]; });
 }
 
-// Grid-stride form (tuning reference): plain loads, one vector per lane.
-template <int OP, typename T, int NLEAF>
-__global__ __launch_bounds__(kBlock) void reduce_tree_vec(TreeArgs a,
-                                                          u32x4 *dst,
-                                                          size_t nvec) {
-  size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-  size_t stride = (size_t)gridDim.x * kBlock;
-  for (; i < nvec; i += stride)
-    st<true>(dst + i, tree_eval<OP, T, u32x4, NLEAF>(a, i));
-}
-
 // Chunked register form: workgroup b owns [b·kBlock·U, (b+1)·kBlock·U),
 // every input read with nt loads (U·nsrc 16-B loads in flight per lane).
 // SAUX = kStoreSc1: the result is written through (buffer stores, sc1).
@@ -101,37 +90,6 @@ __global__ __launch_bounds__(kBlock) void reduce_tree_chunk(TreeArgs a,
       }
     }
   }
-}
-
-// Tapered chunk form (variant 12, the combine's tapered tail applied to the
-// tree): workgroups [0, head) take U = 2 vectors per lane up to vector
-// `split`, the rest — dispatched last — one vector per lane, so the waves that
-// end the launch are shorter.  Write-through stores (the chunk form's sc1).
-template <int OP, typename T, int NLEAF, int U>
-__device__ __forceinline__ void tree_chunk_at(const TreeArgs &a, u32x4 *dst, size_t nvec,
-                                              size_t wg0) {
-#pragma unroll
-  for (int u = 0; u < U; u++) {
-    const size_t i = wg0 + (size_t)u * kBlock + threadIdx.x;
-    if (i < nvec) {
-      u32x4 v = tree_eval_with<OP, T, u32x4, NLEAF>(
-          a, [&](int k) { return ld<true>((const u32x4 *)a.in[k] + i); });
-      const size_t wb = wg0 + (size_t)u * kBlock + (size_t)wave_id() * 64;
-      __builtin_amdgcn_raw_buffer_store_b128(
-          v, __builtin_amdgcn_make_buffer_rsrc(dst + wb, 0, 64 * 16, 0x00020000),
-          (threadIdx.x % 64) * 16, 0, kStoreSc1);
-    }
-  }
-}
-
-template <int OP, typename T, int NLEAF>
-__global__ __launch_bounds__(kBlock) void reduce_tree_taper(TreeArgs a, u32x4 *dst, size_t nvec,
-                                                            size_t split, unsigned head) {
-  const unsigned b = blockIdx.x;
-  if (b < head)
-    tree_chunk_at<OP, T, NLEAF, 2>(a, dst, split, (size_t)b * (kBlock * 2));
-  else
-    tree_chunk_at<OP, T, NLEAF, 1>(a, dst, nvec, split + (size_t)(b - head) * kBlock);
 }
 
 // LDS-DMA form: each wave DMAs U KiB of every input into its own LDS slots
@@ -167,24 +125,6 @@ __global__ __launch_bounds__(W * 64) void reduce_tree_lds(TreeArgs a, int nin,
                    return ld<true>((const u32x4 *)a.in[k] + i);
                  }));
     }
-  }
-}
-
-// Wave-contiguous register form: wave w of workgroup b owns U consecutive KiB
-// of every input (longer DRAM bursts per input stream than the chunked form).
-template <int OP, typename T, int NLEAF, int U>
-__global__ __launch_bounds__(kBlock) void reduce_tree_wave(TreeArgs a,
-                                                           u32x4 *dst,
-                                                           size_t nvec) {
-  const unsigned w = threadIdx.x / 64, l = threadIdx.x % 64;
-  const size_t base = (size_t)blockIdx.x * (kBlock * U) + (size_t)w * 64 * U + l;
-#pragma unroll
-  for (int u = 0; u < U; u++) {
-    size_t i = base + (size_t)u * 64;
-    if (i < nvec)
-      st<true>(dst + i, tree_eval_with<OP, T, u32x4, NLEAF>(a, [&](int k) {
-                 return ld<true>((const u32x4 *)a.in[k] + i);
-               }));
   }
 }
 

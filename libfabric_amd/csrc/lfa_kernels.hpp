@@ -1,10 +1,12 @@
 // lfa_kernels.hpp — the gfx950 combine kernels and their host launchers.
 //
 // Included by lfa_combine.hip (the product entry points of liblfa.so, one
-// object per write op) and by lfa_tune.hip (the on-GPU A/B sweep of
-// bench.py --tune*, built into the separate liblfa_tune.so).  Templates only:
-// a kernel form is compiled into a library only where a launcher
-// instantiates it, so the tuning forms never reach liblfa.so.
+// object per write op) and by lfa_tune.hip, lfa_tune_b.hip and lfa_probe.hip
+// (the on-GPU A/B sweeps of bench.py --tune*, built into the separate
+// liblfa_tune.so).  Every kernel form here is one the product can launch,
+// apart from template arguments only the tuning library passes (UW = false,
+// a forced tile); the forms only the tuning library runs live in
+// lfa_tune_forms.hpp, which no product object includes.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,6 +18,7 @@
 
 #include "lfa_ops.hpp"
 #include "lfa_signal.h"
+#include "lfa_split.h"
 #include "../../include/lfa_atomic.h"
 
 namespace lfa {
@@ -116,32 +119,6 @@ __device__ __forceinline__ u32x4 apply_vec(u32x4 d, u32x4 s) {
 // ---------------------------------------------------------------------------
 constexpr int kBlock = 256;  // 4 waves of 64
 
-// Chunked: workgroup b owns vectors [b·kBlock·U, (b+1)·kBlock·U); step u of
-// thread t touches base + u·kBlock + t, i.e. each wave-instruction reads 1 KiB
-// of consecutive bytes.  All 2·U loads issue before the first op.
-template <int OP, typename T, int U, bool NTL, bool NTS>
-__global__ __launch_bounds__(kBlock) void combine_vec(
-    u32x4 *__restrict__ dst, const u32x4 *__restrict__ src, size_t nvec) {
-  const size_t base = (size_t)blockIdx.x * (kBlock * U) + threadIdx.x;
-  if (base + (size_t)(U - 1) * kBlock < nvec) {  // full chunk: no guards
-    u32x4 a[U], b[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) a[u] = ld<NTL>(dst + base + u * kBlock);
-#pragma unroll
-    for (int u = 0; u < U; u++) b[u] = ld<NTL>(src + base + u * kBlock);
-#pragma unroll
-    for (int u = 0; u < U; u++)
-      st<NTS>(dst + base + u * kBlock, apply_vec<OP, T>(a[u], b[u]));
-  } else {
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      size_t i = base + (size_t)u * kBlock;
-      if (i < nvec)
-        st<NTS>(dst + i, apply_vec<OP, T>(ld<NTL>(dst + i), ld<NTL>(src + i)));
-    }
-  }
-}
-
 // LDS-DMA staged form — the PRODUCT body (bench.py --tune, DESIGN.md
 // "Kernel tuning": 1-2 % faster than register staging at 256 MiB).  Each wave
 // owns U consecutive KiB of both operands and moves them HBM -> LDS with
@@ -174,8 +151,8 @@ __device__ __forceinline__ void wait_vmcnt() {
 // has landed — in issue order the loads of u+1..U-1 (2 each, or 1 each for
 // ATOMIC_WRITE, which reads no dst) and the u stores already issued may stay
 // in flight — then combine and store vector u while the later loads arrive.
-template <int OP, typename T, int U, int SAUX, int u>
-__device__ __forceinline__ void combine_drain(u32x4 (*lds)[kLdsWaves][U][64], unsigned w,
+template <int OP, typename T, int U, int UA, int SAUX, int u>
+__device__ __forceinline__ void combine_drain(u32x4 (*lds)[kLdsWaves][UA][64], unsigned w,
                                               unsigned l, u32x4 *dst,
                                               __amdgpu_buffer_rsrc_t r) {
   if constexpr (u < U) {
@@ -188,10 +165,15 @@ __device__ __forceinline__ void combine_drain(u32x4 (*lds)[kLdsWaves][U][64], un
       st<true>(dst + u * 64 + l, v);
     else
       __builtin_amdgcn_raw_buffer_store_b128(v, r, (unsigned)(u * 64 + l) * 16, 0, SAUX);
-    combine_drain<OP, T, U, SAUX, u + 1>(lds, w, l, dst, r);
+    combine_drain<OP, T, U, UA, SAUX, u + 1>(lds, w, l, dst, r);
   }
 }
 
+// One wave's tile of U KiB per operand from vector `base`: the only place
+// the binary combine's LDS-DMA tile is written (combine_lds,
+// combine_lds_taper, combine_iov).  UA is the tile extent of the LDS array.
+// The loads of all 2·U KiB issue, the wave waits vmcnt(0), then combines and
+// stores; a tile that runs past nvec takes the guarded register path.
 // DRAIN: the wave's loads issue pairwise (dst u, src u, dst u+1, ...) and
 // step u stores vector u as soon as its pair has landed (combine_drain),
 // instead of waiting vmcnt(0) for the whole 2·U KiB before the first store.
@@ -199,14 +181,11 @@ __device__ __forceinline__ void combine_drain(u32x4 (*lds)[kLdsWaves][U][64], un
 // profiles/r03_tune_combine_backtoback.log): 119.4 us against 120.7 us; no
 // change within noise at 32-128 MiB (write-through stores there), so the
 // product drains on the nt-store path only.
-template <int OP, typename T, int U, int SAUX, bool UW = true,
-          bool DRAIN = SAUX == kStoreNt>
-__global__ __launch_bounds__(kLdsWaves * 64) void combine_lds(
-    u32x4 *__restrict__ dst, const u32x4 *__restrict__ src, size_t nvec) {
-  __shared__ u32x4 lds[2][kLdsWaves][U][64];
-  const unsigned w = wave_id<UW>(), l = threadIdx.x % 64;
-  const size_t base =
-      (size_t)blockIdx.x * (kLdsWaves * 64 * U) + (size_t)w * 64 * U;
+template <int OP, typename T, int U, int UA, int SAUX, bool DRAIN = false>
+__device__ __forceinline__ void lds_tile(u32x4 *__restrict__ dst, const u32x4 *__restrict__ src,
+                                         size_t nvec, size_t base,
+                                         u32x4 (*lds)[kLdsWaves][UA][64], unsigned w,
+                                         unsigned l) {
   if (base + 64 * U <= nvec) {
     if constexpr (DRAIN) {
 #pragma unroll
@@ -218,37 +197,37 @@ __global__ __launch_bounds__(kLdsWaves * 64) void combine_lds(
         __builtin_amdgcn_global_load_lds((const void *)(src + base + u * 64 + l),
                                          (lds_void *)&lds[1][w][u][0], 16, 0, 2);
       }
-      const __amdgpu_buffer_rsrc_t r =
-          __builtin_amdgcn_make_buffer_rsrc(dst + base, 0, 64 * U * 16, 0x00020000);
-      combine_drain<OP, T, U, SAUX, 0>(lds, w, l, dst + base, r);
-      return;
-    }
-    if constexpr (OP != OP_WRITE) {  // ATOMIC_WRITE never reads dst
+    } else {
+      if constexpr (OP != OP_WRITE) {  // ATOMIC_WRITE never reads dst
+#pragma unroll
+        for (int u = 0; u < U; u++)
+          __builtin_amdgcn_global_load_lds((const void *)(dst + base + u * 64 + l),
+                                           (lds_void *)&lds[0][w][u][0], 16, 0, /*aux: nt*/ 2);
+      }
 #pragma unroll
       for (int u = 0; u < U; u++)
-        __builtin_amdgcn_global_load_lds((const void *)(dst + base + u * 64 + l),
-                                         (lds_void *)&lds[0][w][u][0], 16, 0,
-                                         /*aux: nt*/ 2);
+        __builtin_amdgcn_global_load_lds((const void *)(src + base + u * 64 + l),
+                                         (lds_void *)&lds[1][w][u][0], 16, 0, 2);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-#pragma unroll
-    for (int u = 0; u < U; u++)
-      __builtin_amdgcn_global_load_lds((const void *)(src + base + u * 64 + l),
-                                       (lds_void *)&lds[1][w][u][0], 16, 0, 2);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // sc1: the wave's tile through one buffer descriptor whose stores carry
     // the bits; nt: plain global stores (0.5 % faster than the buffer form
     // at 256 MiB in rocprofv3)
     const __amdgpu_buffer_rsrc_t r =
         __builtin_amdgcn_make_buffer_rsrc(dst + base, 0, 64 * U * 16, 0x00020000);
+    if constexpr (DRAIN) {
+      combine_drain<OP, T, U, UA, SAUX, 0>(lds, w, l, dst + base, r);
+    } else {
 #pragma unroll
-    for (int u = 0; u < U; u++) {
-      u32x4 v;
-      if constexpr (OP == OP_WRITE) v = lds[1][w][u][l];
-      else v = apply_vec<OP, T>(lds[0][w][u][l], lds[1][w][u][l]);
-      if constexpr (SAUX == kStoreNt)
-        st<true>(dst + base + u * 64 + l, v);
-      else
-        __builtin_amdgcn_raw_buffer_store_b128(v, r, (unsigned)(u * 64 + l) * 16, 0, SAUX);
+      for (int u = 0; u < U; u++) {
+        u32x4 v;
+        if constexpr (OP == OP_WRITE) v = lds[1][w][u][l];
+        else v = apply_vec<OP, T>(lds[0][w][u][l], lds[1][w][u][l]);
+        if constexpr (SAUX == kStoreNt)
+          st<true>(dst + base + u * 64 + l, v);
+        else
+          __builtin_amdgcn_raw_buffer_store_b128(v, r, (unsigned)(u * 64 + l) * 16, 0, SAUX);
+      }
     }
   } else {
     for (int u = 0; u < U; u++) {
@@ -257,6 +236,18 @@ __global__ __launch_bounds__(kLdsWaves * 64) void combine_lds(
         st<true>(dst + i, apply_vec<OP, T>(ld<true>(dst + i), ld<true>(src + i)));
     }
   }
+}
+
+// The uniform grid: workgroup b's wave w owns the tile at (4·b + w)·64·U.
+// UW = false: the divergent wave index (wave_id), for liblfa_tune.so's A/B.
+template <int OP, typename T, int U, int SAUX, bool UW = true,
+          bool DRAIN = SAUX == kStoreNt>
+__global__ __launch_bounds__(kLdsWaves * 64) void combine_lds(
+    u32x4 *__restrict__ dst, const u32x4 *__restrict__ src, size_t nvec) {
+  __shared__ u32x4 lds[2][kLdsWaves][U][64];
+  const unsigned w = wave_id<UW>(), l = threadIdx.x % 64;
+  lds_tile<OP, T, U, U, SAUX, DRAIN>(
+      dst, src, nvec, (size_t)blockIdx.x * (kLdsWaves * 64 * U) + (size_t)w * 64 * U, lds, w, l);
 }
 
 // Tapered tail.  Per-wave timestamps (tools/probe_ramp.py)
@@ -269,44 +260,6 @@ __global__ __launch_bounds__(kLdsWaves * 64) void combine_lds(
 // waves cost more than the drain saves (tools/tune_combine.py variants 85-88,
 // profiles/r04_tune_combine_taper*.json: 32 MiB -1.9 %, 48 and 64 MiB -1.3 %,
 // 16 MiB +2.1 %, 256 MiB on the nt path +1 %).
-template <int OP, typename T, int U, int UA, int SAUX>
-__device__ __forceinline__ void lds_tile(u32x4 *__restrict__ dst, const u32x4 *__restrict__ src,
-                                         size_t nvec, size_t base,
-                                         u32x4 (*lds)[kLdsWaves][UA][64], unsigned w,
-                                         unsigned l) {
-  if (base + 64 * U <= nvec) {
-    if constexpr (OP != OP_WRITE) {  // ATOMIC_WRITE never reads dst
-#pragma unroll
-      for (int u = 0; u < U; u++)
-        __builtin_amdgcn_global_load_lds((const void *)(dst + base + u * 64 + l),
-                                         (lds_void *)&lds[0][w][u][0], 16, 0, /*aux: nt*/ 2);
-    }
-#pragma unroll
-    for (int u = 0; u < U; u++)
-      __builtin_amdgcn_global_load_lds((const void *)(src + base + u * 64 + l),
-                                       (lds_void *)&lds[1][w][u][0], 16, 0, 2);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const __amdgpu_buffer_rsrc_t r =
-        __builtin_amdgcn_make_buffer_rsrc(dst + base, 0, 64 * U * 16, 0x00020000);
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      u32x4 v;
-      if constexpr (OP == OP_WRITE) v = lds[1][w][u][l];
-      else v = apply_vec<OP, T>(lds[0][w][u][l], lds[1][w][u][l]);
-      if constexpr (SAUX == kStoreNt)
-        st<true>(dst + base + u * 64 + l, v);
-      else
-        __builtin_amdgcn_raw_buffer_store_b128(v, r, (unsigned)(u * 64 + l) * 16, 0, SAUX);
-    }
-  } else {
-    for (int u = 0; u < U; u++) {
-      size_t i = base + (size_t)u * 64 + l;
-      if (i < nvec)
-        st<true>(dst + i, apply_vec<OP, T>(ld<true>(dst + i), ld<true>(src + i)));
-    }
-  }
-}
-
 template <int OP, typename T, int U, int SAUX>
 __global__ __launch_bounds__(kLdsWaves * 64) void combine_lds_taper(
     u32x4 *__restrict__ dst, const u32x4 *__restrict__ src, size_t nvec, size_t split,
@@ -321,31 +274,6 @@ __global__ __launch_bounds__(kLdsWaves * 64) void combine_lds_taper(
     lds_tile<OP, T, 1, U, SAUX>(dst, src, nvec,
                                 split + (size_t)(b - head) * (kLdsWaves * 64) + (size_t)w * 64,
                                 lds, w, l);
-}
-
-// Grid-stride variant (for the tuning sweep): a fixed grid of G workgroups
-// walks the buffer; each thread holds U vectors spaced kBlock apart.
-template <int OP, typename T, int U, bool NTL, bool NTS>
-__global__ __launch_bounds__(kBlock) void combine_vec_gs(
-    u32x4 *__restrict__ dst, const u32x4 *__restrict__ src, size_t nvec) {
-  const size_t step = (size_t)gridDim.x * kBlock * U;
-  size_t base = (size_t)blockIdx.x * (kBlock * U) + threadIdx.x;
-  for (; base + (size_t)(U - 1) * kBlock < nvec; base += step) {
-    u32x4 a[U], b[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) a[u] = ld<NTL>(dst + base + u * kBlock);
-#pragma unroll
-    for (int u = 0; u < U; u++) b[u] = ld<NTL>(src + base + u * kBlock);
-#pragma unroll
-    for (int u = 0; u < U; u++)
-      st<NTS>(dst + base + u * kBlock, apply_vec<OP, T>(a[u], b[u]));
-  }
-#pragma unroll
-  for (int u = 0; u < U; u++) {
-    size_t i = base + (size_t)u * kBlock;
-    if (i < nvec)
-      st<NTS>(dst + i, apply_vec<OP, T>(ld<NTL>(dst + i), ld<NTL>(src + i)));
-  }
 }
 
 // ---------------------------------------------------------------------------

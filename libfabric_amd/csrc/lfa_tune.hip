@@ -1,6 +1,7 @@
 // lfa_tune.hip — alternative schedules of the headline kernel (float FI_SUM
 // combine) for the on-GPU A/B sweep (bench.py --tune).  Not on the product
-// path: the winner is folded back into combine_vec (lfa_combine.hip).
+// path: a winner is folded back into the product body (lds_tile / combine_lds,
+// lfa_kernels.hpp).
 //
 // Each variant is the same dst[i] += src[i] stream over 16-byte vectors; they
 // differ only in how work maps to lanes, cache policy and staging:
@@ -15,7 +16,7 @@
 #include <string.h>
 #include <time.h>
 
-#include "lfa_kernels.hpp"
+#include "lfa_tune_forms.hpp"
 
 namespace lfa_tune {
 
@@ -314,7 +315,7 @@ static void taper(u32x4 *d, const u32x4 *v, size_t nvec, size_t s2, size_t s1,
 
 using namespace lfa_tune;
 
-// Variants 12.. (0..11 live in lfa_combine.hip next to the product kernel).
+// Variants 12.. (0..11: lfa__tune_sum_f32 below, the lfa_tune_forms.hpp kernels).
 extern "C" int lfa__tune2_sum_f32(int variant, void *dst, const void *src,
                                   size_t nvec, void *stream) {
   hipStream_t s = (hipStream_t)stream;
@@ -403,7 +404,7 @@ extern "C" int lfa__tune2_sum_f32(int variant, void *dst, const void *src,
   }
 #undef RUN
 #undef LDSDMA
-  return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO;
+  return lfa::launch_rc();
 }
 
 // ---------------------------------------------------------------------------
@@ -414,7 +415,8 @@ namespace lfa {
 
 // Tree vector bodies the product does not ship: grid-stride plain loads (0),
 // LDS-DMA with 4/2/1 waves (4-6), wave-contiguous U=2/4 (7-8), chunked sc1
-// U=1/2 (9-10); anything else is the product's own choice.
+// U=1/2 (9-10), the forms of launch_tree_tune_form (lfa_tune_forms.hpp);
+// anything else is the product's own choice.
 struct TuneTreeBody {
   template <int OP, typename T, int NLEAF>
   static void launch(const TreeArgs &b, int nsrc, u32x4 *dst, size_t nvec,
@@ -449,7 +451,8 @@ struct TuneTreeBody {
                            dim3(kBlock), 0, s, b, dst, nvec);
         return;
       default:
-        launch_tree_body<OP, T, NLEAF, true>(b, nsrc, dst, nvec, s, variant);
+        if (!launch_tree_tune_form<OP, T, NLEAF>(b, nsrc, dst, nvec, s, variant))
+          launch_tree_body<OP, T, NLEAF>(b, nsrc, dst, nvec, s, variant);
     }
   }
 };
@@ -488,7 +491,7 @@ extern "C" int lfa__tune_sum_f32(int variant, void *dst, const void *src,
     case 11: chunk(combine_vec<OP_SUM, float, 8, false, false>, 8); break;
     default: return -LFA_EINVAL;
   }
-  return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO;
+  return lfa::launch_rc();
 }
 
 // Tree-kernel sweep: float SUM over `nsrc` device inputs; -1 = the product.
@@ -1037,18 +1040,14 @@ extern "C" int lfa__tune_treeput_f32(int variant, void *const *dsts, int ndst,
     case 58: TPX(4, 19, 1); break;        // G = 1: the remap alone
 #undef TPX
     case 64: case 65: {                   // the wide form with a 1-KiB tail: 1/4, 1/8
-      const size_t div = variant == 64 ? 4 : 8, hv = (size_t)kBlock * 2;
-      size_t split = nvec - nvec / div;
-      split -= split % hv;
-      const unsigned head = (unsigned)(split / hv);
-      const unsigned tail = (unsigned)((nvec - split + kBlock - 1) / kBlock);
-      hipLaunchKernelGGL((tp_taper<2>), dim3(head + tail), dim3(kBlock), kPutNarrowLds, s, a,
-                         nvec, split, head);
+      const lfa_taper tp = lfa_split_taper(nvec, variant == 64 ? 4 : 8, (size_t)kBlock * 2, kBlock);
+      hipLaunchKernelGGL((tp_taper<2>), dim3(tp.nhead + tp.ntail), dim3(kBlock), kPutNarrowLds,
+                         s, a, nvec, tp.split, tp.nhead);
       break;
     }
     default: return -LFA_EINVAL;
   }
 #undef TP
 #undef TPP
-  return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO;
+  return lfa::launch_rc();
 }

@@ -9,7 +9,7 @@
 #include <string.h>
 #include <time.h>
 
-#include "lfa_kernels.hpp"
+#include "lfa_tune_forms.hpp"
 
 // ---------------------------------------------------------------------------
 // Compare body with its third input in registers: CSWAP's
@@ -109,14 +109,10 @@ extern "C" int lfa__tune_fetch_f32(int variant, int swap, void *dst, const void 
       case 20: case 21: {
         // the write-through (sc1) body with a 1-KiB tapered tail, as the
         // combine has from 32 MiB: the last 1/8 (20) or 1/4 (21)
-        const size_t div = variant == 20 ? 8 : 4;
-        const size_t hv = (size_t)kLdsWaves * 64 * 4, tv = (size_t)kLdsWaves * 64;
-        size_t split = nvec - nvec / div;
-        split -= split % hv;
-        const unsigned head = (unsigned)(split / hv);
-        const unsigned tail = (unsigned)((nvec - split + tv - 1) / tv);
-        hipLaunchKernelGGL((fetch_lds_taper<4, 1, kStoreSc1, FF>), dim3(head + tail),
-                           dim3(kLdsWaves * 64), 0, s, f, nvec, split, head);
+        const lfa_taper tp = lfa_split_taper(nvec, variant == 20 ? 8 : 4,
+                                             (size_t)kLdsWaves * 64 * 4, kLdsWaves * 64);
+        hipLaunchKernelGGL((fetch_lds_taper<4, 1, kStoreSc1, FF>), dim3(tp.nhead + tp.ntail),
+                           dim3(kLdsWaves * 64), 0, s, f, nvec, tp.split, tp.nhead);
         break;
       }
       case 14: case 15: case 16: case 17: case 18: case 19: {
@@ -128,13 +124,10 @@ extern "C" int lfa__tune_fetch_f32(int variant, int swap, void *dst, const void 
                            variant == 18 ? 2 : 8;
         auto taper = [&](auto ut) {
           constexpr int UT = decltype(ut)::value;
-          const size_t hv = (size_t)kLdsWaves * 64 * 4, tv = (size_t)kLdsWaves * 64 * UT;
-          size_t split = nvec - nvec / div;
-          split -= split % hv;
-          const unsigned head = (unsigned)(split / hv);
-          const unsigned tail = (unsigned)((nvec - split + tv - 1) / tv);
-          hipLaunchKernelGGL((fetch_lds_taper<4, UT, kStoreNt, FF>), dim3(head + tail),
-                             dim3(kLdsWaves * 64), 0, s, f, nvec, split, head);
+          const lfa_taper tp = lfa_split_taper(nvec, div, (size_t)kLdsWaves * 64 * 4,
+                                               (size_t)kLdsWaves * 64 * UT);
+          hipLaunchKernelGGL((fetch_lds_taper<4, UT, kStoreNt, FF>), dim3(tp.nhead + tp.ntail),
+                             dim3(kLdsWaves * 64), 0, s, f, nvec, tp.split, tp.nhead);
         };
         if (variant == 15 || variant == 19) taper(I2());
         else taper(I1());
@@ -157,7 +150,7 @@ extern "C" int lfa__tune_fetch_f32(int variant, int swap, void *dst, const void 
         return -LFA_EINVAL;
       default: return -LFA_EINVAL;
     }
-    return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO;
+    return lfa::launch_rc();
   };
   if (swap)
     return go(SwapF<OP_CSWAP, float, true>{(char *)dst, (const char *)src,
@@ -249,7 +242,7 @@ extern "C" int lfa__tune_read_n(const void *const *ins, int nin, void *sink, siz
     case 16: hipLaunchKernelGGL((read_chunk<16>), grid, block, 0, s, a, (u32x4 *)sink, nvec); break;
     default: return -LFA_EINVAL;
   }
-  return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO;
+  return lfa::launch_rc();
 }
 
 // kind 0: read a; 1: read a and b; 2: write dst, nt; 3: write dst, sc1.
@@ -280,7 +273,7 @@ extern "C" int lfa__tune_stream(int kind, void *dst, const void *a, const void *
     default:
       return -LFA_EINVAL;
   }
-  return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO;
+  return lfa::launch_rc();
 }
 
 // ---------------------------------------------------------------------------
@@ -499,41 +492,7 @@ static void launch_dyn(u32x4 *d, const u32x4 *v, size_t nvec, hipStream_t s) {
 // over ~2.4 us at 32 MiB.  Here the last `tail` vectors go to workgroups
 // whose waves own UT < UH KiB each, dispatched last (the highest block ids),
 // so the waves still running at the end are shorter ones.
-template <int UH, int UT, int SAUX>
-__device__ __forceinline__ void taper_tile(u32x4 *__restrict__ dst,
-                                           const u32x4 *__restrict__ src, size_t nvec,
-                                           size_t base, u32x4 (*lds)[kLdsWaves][UH][64],
-                                           unsigned w, unsigned l) {
-  constexpr int U = UT;
-  if (base + 64 * U <= nvec) {
-#pragma unroll
-    for (int u = 0; u < U; u++)
-      __builtin_amdgcn_global_load_lds((const void *)(dst + base + u * 64 + l),
-                                       (lds_void *)&lds[0][w][u][0], 16, 0, 2);
-#pragma unroll
-    for (int u = 0; u < U; u++)
-      __builtin_amdgcn_global_load_lds((const void *)(src + base + u * 64 + l),
-                                       (lds_void *)&lds[1][w][u][0], 16, 0, 2);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const __amdgpu_buffer_rsrc_t r =
-        __builtin_amdgcn_make_buffer_rsrc(dst + base, 0, 64 * U * 16, 0x00020000);
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      u32x4 v = apply_vec<OP_SUM, float>(lds[0][w][u][l], lds[1][w][u][l]);
-      if constexpr (SAUX == kStoreNt)
-        st<true>(dst + base + u * 64 + l, v);
-      else
-        __builtin_amdgcn_raw_buffer_store_b128(v, r, (unsigned)(u * 64 + l) * 16, 0, SAUX);
-    }
-  } else {
-    for (int u = 0; u < U; u++) {
-      size_t i = base + (size_t)u * 64 + l;
-      if (i < nvec)
-        st<true>(dst + i, apply_vec<OP_SUM, float>(ld<true>(dst + i), ld<true>(src + i)));
-    }
-  }
-}
-
+// Both kinds of tile are the product's (lds_tile, lfa_kernels.hpp).
 template <int UH, int UT, int SAUX>
 __global__ __launch_bounds__(kLdsWaves * 64) void combine_taper(u32x4 *__restrict__ dst,
                                                                const u32x4 *__restrict__ src,
@@ -543,32 +502,30 @@ __global__ __launch_bounds__(kLdsWaves * 64) void combine_taper(u32x4 *__restric
   const unsigned w = wave_id<true>(), l = threadIdx.x % 64;
   const unsigned b = blockIdx.x;
   if (b < head_blocks)
-    taper_tile<UH, UH, SAUX>(dst, src, split,
-                             (size_t)b * (kLdsWaves * 64 * UH) + (size_t)w * 64 * UH, lds, w, l);
+    lds_tile<OP_SUM, float, UH, UH, SAUX>(
+        dst, src, split, (size_t)b * (kLdsWaves * 64 * UH) + (size_t)w * 64 * UH, lds, w, l);
   else
-    taper_tile<UH, UT, SAUX>(dst, src, nvec,
-                             split + (size_t)(b - head_blocks) * (kLdsWaves * 64 * UT) +
-                                 (size_t)w * 64 * UT,
-                             lds, w, l);
+    lds_tile<OP_SUM, float, UT, UH, SAUX>(
+        dst, src, nvec,
+        split + (size_t)(b - head_blocks) * (kLdsWaves * 64 * UT) + (size_t)w * 64 * UT, lds, w,
+        l);
 }
 
 template <int UH, int UT>
 static void launch_taper(u32x4 *d, const u32x4 *v, size_t nvec, unsigned tail_div,
                          hipStream_t s) {
-  const size_t hv = (size_t)kLdsWaves * 64 * UH, tv = (size_t)kLdsWaves * 64 * UT;
-  size_t split = nvec - nvec / tail_div;
-  split -= split % hv;
-  const unsigned head = (unsigned)(split / hv);
-  const unsigned tail = (unsigned)((nvec - split + tv - 1) / tv);
+  const lfa_taper tp = lfa_split_taper(nvec, tail_div, (size_t)kLdsWaves * 64 * UH,
+                                       (size_t)kLdsWaves * 64 * UT);
+  const dim3 grid(tp.nhead + tp.ntail);
   if (nvec * 16 < kSc1Bytes)
-    hipLaunchKernelGGL((combine_taper<UH, UT, kStoreSc1>), dim3(head + tail),
-                       dim3(kLdsWaves * 64), 0, s, d, v, nvec, split, head);
+    hipLaunchKernelGGL((combine_taper<UH, UT, kStoreSc1>), grid, dim3(kLdsWaves * 64), 0, s, d,
+                       v, nvec, tp.split, tp.nhead);
   else
-    hipLaunchKernelGGL((combine_taper<UH, UT, kStoreNt>), dim3(head + tail),
-                       dim3(kLdsWaves * 64), 0, s, d, v, nvec, split, head);
+    hipLaunchKernelGGL((combine_taper<UH, UT, kStoreNt>), grid, dim3(kLdsWaves * 64), 0, s, d, v,
+                       nvec, tp.split, tp.nhead);
 }
 
-// The product's drained nt body (combine_lds<..., DRAIN>) with a tapered tail
+// The product's drained nt body (lds_tile<..., DRAIN>) with a tapered tail
 // (round 6): round 4's taper variants 85-89 ran their head tiles on the
 // undrained body, so their +1 % at 256 MiB mixed two changes; the fetch
 // kernel's drained head + 1-KiB tail at div 4 gained ~1 % (fetch_lds_taper).
@@ -579,38 +536,26 @@ __global__ __launch_bounds__(kLdsWaves * 64) void combine_taper_drained(
   __shared__ u32x4 lds[2][kLdsWaves][U][64];
   const unsigned w = wave_id<true>(), l = threadIdx.x % 64;
   const unsigned b = blockIdx.x;
-  if (b < head_blocks) {
-    const size_t base = (size_t)b * (kLdsWaves * 64 * U) + (size_t)w * 64 * U;
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      __builtin_amdgcn_global_load_lds((const void *)(dst + base + u * 64 + l),
-                                       (lds_void *)&lds[0][w][u][0], 16, 0, 2);
-      __builtin_amdgcn_global_load_lds((const void *)(src + base + u * 64 + l),
-                                       (lds_void *)&lds[1][w][u][0], 16, 0, 2);
-    }
-    const __amdgpu_buffer_rsrc_t r =
-        __builtin_amdgcn_make_buffer_rsrc(dst + base, 0, 64 * U * 16, 0x00020000);
-    combine_drain<OP_SUM, float, U, SAUX, 0>(lds, w, l, dst + base, r);
-    return;
-  }
-  taper_tile<U, 1, SAUX>(dst, src, nvec,
-                         split + (size_t)(b - head_blocks) * (kLdsWaves * 64) + (size_t)w * 64,
-                         lds, w, l);
+  if (b < head_blocks)
+    lds_tile<OP_SUM, float, U, U, SAUX, true>(
+        dst, src, split, (size_t)b * (kLdsWaves * 64 * U) + (size_t)w * 64 * U, lds, w, l);
+  else
+    lds_tile<OP_SUM, float, 1, U, SAUX>(
+        dst, src, nvec, split + (size_t)(b - head_blocks) * (kLdsWaves * 64) + (size_t)w * 64,
+        lds, w, l);
 }
 
 static void launch_taper_drained(u32x4 *d, const u32x4 *v, size_t nvec, size_t div,
                                  hipStream_t s) {
-  const size_t hv = (size_t)kLdsWaves * 64 * 4, tv = (size_t)kLdsWaves * 64;
-  size_t split = nvec - nvec / div;
-  split -= split % hv;
-  const unsigned head = (unsigned)(split / hv);
-  const unsigned tail = (unsigned)((nvec - split + tv - 1) / tv);
+  const lfa_taper tp =
+      lfa_split_taper(nvec, div, (size_t)kLdsWaves * 64 * 4, (size_t)kLdsWaves * 64);
+  const dim3 grid(tp.nhead + tp.ntail);
   if (nvec * 16 < kSc1Bytes)
-    hipLaunchKernelGGL((combine_taper_drained<4, kStoreSc1>), dim3(head + tail),
-                       dim3(kLdsWaves * 64), 0, s, d, v, nvec, split, head);
+    hipLaunchKernelGGL((combine_taper_drained<4, kStoreSc1>), grid, dim3(kLdsWaves * 64), 0, s,
+                       d, v, nvec, tp.split, tp.nhead);
   else
-    hipLaunchKernelGGL((combine_taper_drained<4, kStoreNt>), dim3(head + tail),
-                       dim3(kLdsWaves * 64), 0, s, d, v, nvec, split, head);
+    hipLaunchKernelGGL((combine_taper_drained<4, kStoreNt>), grid, dim3(kLdsWaves * 64), 0, s, d,
+                       v, nvec, tp.split, tp.nhead);
 }
 
 // Statically balanced resident grid: exactly one round of
@@ -872,7 +817,7 @@ extern "C" int lfa__tune3_sum_f32(int variant, void *dst, const void *src, size_
       break;
     default: return -LFA_EINVAL;
   }
-  return hipGetLastError() == hipSuccess ? 0 : -LFA_EIO;
+  return lfa::launch_rc();
 }
 
 // ---------------------------------------------------------------------------
