@@ -63,7 +63,7 @@ def build_lfa(jobs: int = 8, verbose: bool = False) -> str:
     for op in WRITE_OPS:
         o = os.path.join(BUILD, f"combine_op{op}.o")
         objs.append(o)
-        if _newer(o, [kern] + hdrs):
+        if _newer(o, [kern, os.path.join(CSRC, "lfa_launch.h")] + hdrs):
             steps.append([HIPCC, *HIP_FLAGS, f"-DLFA_OP={op}", "-c", kern, "-o", o])
     # tuning-only kernel forms (bench.py --tune*): their own library
     tune_objs = []
@@ -118,14 +118,25 @@ def build_lfa(jobs: int = 8, verbose: bool = False) -> str:
         steps.append(["g++", "-O2", "-fPIC", "-std=c++17", "-Wall",
                       "-D__HIP_PLATFORM_AMD__", "-I" + INC,
                       "-I" + os.path.join(ROCM, "include"), "-c", direct, "-o", o])
-    capi = os.path.join(CSRC, "lfa_capi.cpp")
-    o = os.path.join(BUILD, "lfa_capi.o")
-    objs.append(o)
-    if _newer(o, [capi] + hdrs):
-        # host-only C++ (hipcc would compile .cpp as HIP): g++ + HIP C API
-        steps.append(["g++", "-O2", "-fPIC", "-std=c++17", "-Wall",
-                      "-D__HIP_PLATFORM_AMD__", "-I" + INC,
-                      "-I" + os.path.join(ROCM, "include"), "-c", capi, "-o", o])
+    # the C ABI's host units, each with the headers it includes: host-only C++
+    # (hipcc would compile .cpp as HIP), so g++ + HIP's C API; the last two
+    # are arithmetic and a registry, and get no HIP include path or define
+    atomic_h = [os.path.join(INC, "lfa_atomic.h"), os.path.join(INC, "lfa_fabric.h")]
+    capi_int = [os.path.join(CSRC, "lfa_capi_int.h"), os.path.join(CSRC, "lfa_launch.h"), *atomic_h]
+    iov_h = [os.path.join(CSRC, f) for f in ("lfa_iov_table.h", "lfa_iov.h", "lfa_split.h")]
+    sig_h = [os.path.join(CSRC, "lfa_signal.h")]
+    hip_host = ["-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROCM, "include")]
+    for name, deps, extra in (("lfa_capi", capi_int + sig_h, hip_host),
+                              ("lfa_stage", capi_int + sig_h, hip_host),
+                              ("lfa_iov", capi_int + iov_h, hip_host),
+                              ("lfa_valid", capi_int, []),
+                              ("lfa_param", atomic_h, [])):
+        src = os.path.join(CSRC, name + ".cpp")
+        o = os.path.join(BUILD, name + ".o")
+        objs.append(o)
+        if _newer(o, [src] + deps):
+            steps.append(["g++", "-O2", "-fPIC", "-std=c++17", "-Wall", *extra, "-I" + INC,
+                          "-c", src, "-o", o])
     host = os.path.join(CSRC, "lfa_host.cpp")
     o = os.path.join(BUILD, "lfa_host.o")
     objs.append(o)

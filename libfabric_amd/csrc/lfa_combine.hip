@@ -33,6 +33,7 @@
 // -ffp-contract=off -DLFA_OP=<op>, once per enum fi_op row (0..18; see
 // libfabric_amd/build.py).
 #include "lfa_kernels.hpp"
+#include "lfa_launch.h"
 
 namespace lfa {
 
@@ -41,11 +42,10 @@ namespace lfa {
 // ---------------------------------------------------------------------------
 // This file is compiled once per write op (-DLFA_OP=<enum fi_op value>) so the
 // ~100 (op, datatype) kernel families build in parallel; each object exports
-//   lfa__write_op<N>(dt, dst, src, cnt, stream)
-//   lfa__tree_op<N>(dt, dst, srcs, nsrc, cnt, stream)
-//   lfa__writev_op<N>(dt, args, ntile, stream)
-//   lfa__treev_op<N>(dt, args, nsrc, ntile, stream)
-// which lfa_capi.cpp dispatches to.  Return 0 or a negative LFA_E* code.
+// one record, lfa__op<N> (struct lfa_op_launch, lfa_launch.h): the launch
+// entries of the forms op N has, NULL for the others.  lfa_capi.cpp gathers
+// the 19 records in kOps and dispatches through them.  The entries return 0
+// or a negative LFA_E* code.
 // Ops whose result bits do not depend on an integer's signedness: wrapping
 // SUM / PROD (the low bits of a two's-complement sum or product), the
 // bitwise and logical ops, READ / WRITE, CSWAP (bitwise compare), CSWAP_NE
@@ -131,42 +131,40 @@ static int by_iov_type(int dt, F &&f) {
 #define LFA_CAT2(a, b) a##b
 #define LFA_CAT(a, b) LFA_CAT2(a, b)
 
-#if LFA_OP <= 11
-#if LFA_OP != 10
-extern "C" int LFA_CAT(lfa__write_op, LFA_OP)(int dt, void *dst,
-                                              const void *src, size_t cnt,
-                                              void *stream) {
-  // dt | LFA_WRITE_MAPPED: operands on their host mappings (lfa_capi.cpp)
+// Which forms op LFA_OP has: each is a function where it does, and a null
+// pointer of the member's type where it does not.
+#if LFA_OP <= 11 && LFA_OP != 10
+static int op_write(int dt, void *dst, const void *src, size_t cnt, void *stream) {
+  // dt | LFA_WRITE_MAPPED: operands on their host mappings (lfa_stage.cpp)
   const bool mapped = (dt & LFA_WRITE_MAPPED) != 0;
   return lfa::by_reduce_type<LFA_OP>(dt & ~LFA_WRITE_MAPPED, [&](auto *tag) {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     return lfa::launch_write<LFA_OP, T>(dst, src, cnt, (hipStream_t)stream, mapped);
   });
 }
-#endif
 
-#if LFA_OP != 10
-extern "C" int LFA_CAT(lfa__writev_op, LFA_OP)(int dt, const lfa_iov_args *a,
-                                               unsigned ntile, void *stream) {
+static int op_writev(int dt, const lfa_iov_args *a, unsigned ntile, void *stream) {
   return lfa::by_iov_type<LFA_OP>(dt, [&](auto *tag) {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     return lfa::launch_writev<LFA_OP, T>(*a, ntile, (hipStream_t)stream);
   });
 }
+#else
+constexpr lfa_launch_write_t op_write = nullptr;
+constexpr lfa_launch_writev_t op_writev = nullptr;
 #endif
 
 #if LFA_OP <= 9
-extern "C" int LFA_CAT(lfa__treev_op, LFA_OP)(int dt, const lfa_iov_args *a, int nsrc,
-                                              unsigned ntile, void *stream) {
+static int op_treev(int dt, const lfa_iov_args *a, int nsrc, unsigned ntile,
+                    void *stream) {
   return lfa::by_reduce_type<LFA_OP>(dt, [&](auto *tag) {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     return lfa::launch_treev<LFA_OP, T>(*a, nsrc, ntile, (hipStream_t)stream);
   });
 }
 
-extern "C" int LFA_CAT(lfa__tree_op, LFA_OP)(int dt, void *dst,
-                                             const void *const *srcs, int nsrc,
-                                             size_t cnt, void *stream) {
+static int op_tree(int dt, void *dst, const void *const *srcs, int nsrc, size_t cnt,
+                   void *stream) {
   return lfa::by_reduce_type<LFA_OP>(dt, [&](auto *tag) {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     return lfa::launch_tree<LFA_OP, T>(dst, srcs, nsrc, cnt,
@@ -174,42 +172,52 @@ extern "C" int LFA_CAT(lfa__tree_op, LFA_OP)(int dt, void *dst,
   });
 }
 
-extern "C" int LFA_CAT(lfa__oneshot_op, LFA_OP)(int dt, const lfa_oneshot *a,
-                                                void *stream) {
+static int op_oneshot(int dt, const lfa_oneshot *a, void *stream) {
   return lfa::by_reduce_type<LFA_OP>(dt, [&](auto *tag) {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     return lfa::launch_oneshot<LFA_OP, T>(*a, (hipStream_t)stream);
   });
 }
 
-extern "C" int LFA_CAT(lfa__treeput_op, LFA_OP)(int dt, void *const *dsts, int ndst,
-                                                const void *const *srcs, int nsrc,
-                                                size_t cnt, void *stream) {
+static int op_treeput(int dt, void *const *dsts, int ndst, const void *const *srcs,
+                      int nsrc, size_t cnt, void *stream) {
   return lfa::by_reduce_type<LFA_OP>(dt, [&](auto *tag) {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     return lfa::launch_tree_put<LFA_OP, T>(dsts, ndst, srcs, nsrc, cnt,
                                            (hipStream_t)stream);
   });
 }
+#else
+constexpr lfa_launch_treev_t op_treev = nullptr;
+constexpr lfa_launch_tree_t op_tree = nullptr;
+constexpr lfa_launch_oneshot_t op_oneshot = nullptr;
+constexpr lfa_launch_treeput_t op_treeput = nullptr;
 #endif
 
-extern "C" int LFA_CAT(lfa__readwrite_op, LFA_OP)(int dt, void *dst,
-                                                  const void *src, void *res,
-                                                  size_t cnt, void *stream) {
+#if LFA_OP <= 11
+static int op_readwrite(int dt, void *dst, const void *src, void *res, size_t cnt,
+                        void *stream) {
   return lfa::by_type<LFA_OP>(dt, [&](auto *tag) {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     return lfa::launch_readwrite<LFA_OP, T>(dst, src, res, cnt,
                                             (hipStream_t)stream);
   });
 }
+constexpr lfa_launch_swap_t op_swap = nullptr;
 #else
-extern "C" int LFA_CAT(lfa__swap_op, LFA_OP)(int dt, void *dst, const void *src,
-                                             const void *cmp, void *res,
-                                             size_t cnt, void *stream) {
+constexpr lfa_launch_readwrite_t op_readwrite = nullptr;
+static int op_swap(int dt, void *dst, const void *src, const void *cmp, void *res,
+                   size_t cnt, void *stream) {
   return lfa::by_type<LFA_OP>(dt, [&](auto *tag) {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     return lfa::launch_swap<LFA_OP, T>(dst, src, cmp, res, cnt,
                                        (hipStream_t)stream);
   });
 }
+#endif
+
+// host data: the device pass would emit a const object too, and has no entries
+#ifndef __HIP_DEVICE_COMPILE__
+extern "C" const lfa_op_launch LFA_CAT(lfa__op, LFA_OP) = {
+    op_write, op_writev, op_tree, op_treev, op_treeput, op_oneshot, op_readwrite, op_swap};
 #endif

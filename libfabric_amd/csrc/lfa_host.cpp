@@ -259,7 +259,7 @@ int lfa_host_reduce_tree(enum lfa_op op, enum lfa_datatype dt, void *dst,
 }
 
 // The list forms' argument check, shared by lfa_host_writev and the device
-// forms of lfa_capi.cpp: everything that makes a call -LFA_EINVAL, found
+// forms of lfa_iov.cpp: everything that makes a call -LFA_EINVAL, found
 // before any element is touched.  `src` may be null (lfa_reduce_treev_async
 // has no src list).  Two dst segments must not share a byte: separate calls
 // would order them, one launch cannot.  The ranges are sorted by start

@@ -1,5 +1,5 @@
 /* lfa_iov.h — the segment table of the list (fi_ioc) forms, shared by the
- * host side that builds it (lfa_capi.cpp) and the kernels that walk it
+ * host side that builds it (lfa_iov_table.h) and the kernels that walk it
  * (lfa_k_iov.hpp).  Plain C: no HIP types.
  *
  * One launch covers every non-empty segment of a call.  The host cuts each

@@ -36,7 +36,7 @@ struct IovTreeArgs {
 constexpr unsigned kIovTileVecs = LFA_IOV_TILE / 16;
 // The fused list form is instantiated up to 8 leaves (2..15 inputs), the
 // fan-ins of a node's GPUs; a wider tree is one lfa_reduce_tree_async per
-// segment (lfa_capi.cpp), which keeps a fifth kernel family of 16- and
+// segment (lfa_iov.cpp), which keeps a fifth kernel family of 16- and
 // 32-leaf bodies out of liblfa.so.
 constexpr int kIovMaxLeaf = LFA_IOV_TREE_LEAVES;
 static_assert(kIovTileVecs == kLdsWaves * 64 * kUnroll, "a tile is one workgroup of lds_tile");
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(kBlock) void reduce_iov(IovTreeArgs ta) {
 }
 
 // ---------------------------------------------------------------------------
-// launchers: the table is built and validated by lfa_capi.cpp
+// launchers: the table is built and validated by lfa_iov.cpp
 // ---------------------------------------------------------------------------
 static_assert(kBlock == kLdsWaves * 64, "one workgroup shape for both forms");
 

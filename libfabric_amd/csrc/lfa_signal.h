@@ -134,13 +134,13 @@ int lfa_oneshot_reduce_async(int op, int datatype, const struct lfa_oneshot *a,
 				void *stream);
 
 /* The address device `device`'s kernels use for p without staging (liblfa,
- * lfa_capi.cpp): pinned or registered host memory through its device mapping,
+ * lfa_stage.cpp): pinned or registered host memory through its device mapping,
  * that device's own memory as it is; NULL for pageable memory, another
  * device's, or LFA_HOST_ZERO_COPY=0.  Never a registration lfa_atomic_write_staged
  * made for one call of its own. */
 void *lfa_zero_copy_addr(const void *p, int device);
 /* Flag on the datatype argument of liblfa's internal per-op write entries
- * (lfa__write_op<N>): the operands are host memory on its device mapping. */
+ * (lfa__op<N>.write, lfa_launch.h): the operands are host memory on its device mapping. */
 #define LFA_WRITE_MAPPED 0x10000
 /* Temporary registrations lfa_atomic_write_staged holds right now (tests:
  * 0 once every call has returned). */

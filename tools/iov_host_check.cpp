@@ -5,10 +5,11 @@
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       -ffp-contract=off -Iinclude tools/iov_host_check.cpp \
-//       libfabric_amd/csrc/lfa_host.cpp -o /tmp/iov_host_check && /tmp/iov_host_check
+//       libfabric_amd/csrc/lfa_host.cpp libfabric_amd/csrc/lfa_valid.cpp \
+//       -o /tmp/iov_host_check && /tmp/iov_host_check
 //
-// lfa_host.cpp asks liblfa.so's C ABI which (datatype, op) pairs exist; the
-// few entries it needs are restated here so the program links without HIP.
+// lfa_host.cpp asks liblfa.so's C ABI which (datatype, op) pairs exist:
+// lfa_valid.cpp, the unit that answers in the library, needs no HIP either.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -18,28 +19,7 @@
 
 #include "lfa_atomic.h"
 
-extern "C" {
-size_t lfa_datatype_size(enum lfa_datatype dt) {
-  static const size_t sz[LFA_DATATYPE_CNT] = {1, 1, 2, 2, 4, 4, 8, 8, 4, 8, 8, 16, 16, 32, 16, 16};
-  return (unsigned)dt < LFA_DATATYPE_CNT ? sz[dt] : 0;
-}
-size_t lfa_reduce_datatype_size(enum lfa_datatype dt) {
-  return dt == LFA_FLOAT16 || dt == LFA_BFLOAT16 ? 2 : lfa_datatype_size(dt);
-}
-int lfa_atomic_valid(enum lfa_datatype dt, enum lfa_op op, uint64_t) {
-  const bool flt = dt == LFA_FLOAT || dt == LFA_DOUBLE || dt == LFA_FLOAT_COMPLEX;
-  const bool known = dt <= LFA_FLOAT_COMPLEX || dt == LFA_INT128 || dt == LFA_UINT128;
-  if (!known || (unsigned)op > LFA_ATOMIC_WRITE || op == LFA_ATOMIC_READ) return -LFA_EOPNOTSUPP;
-  if (flt && (op == LFA_BOR || op == LFA_BAND || op == LFA_BXOR)) return -LFA_EOPNOTSUPP;
-  if (dt == LFA_FLOAT_COMPLEX && (op == LFA_MIN || op == LFA_MAX)) return -LFA_EOPNOTSUPP;
-  return 0;
-}
-int lfa_reduce_valid(enum lfa_datatype dt, enum lfa_op op) {
-  if (dt == LFA_FLOAT16 || dt == LFA_BFLOAT16) return lfa_atomic_valid(LFA_FLOAT, op, 0);
-  return lfa_atomic_valid(dt, op, 0);
-}
-int lfa__iov_check(const struct lfa_ioc *, const struct lfa_ioc *, int, size_t, size_t);
-}
+extern "C" int lfa__iov_check(const struct lfa_ioc *, const struct lfa_ioc *, int, size_t, size_t);
 
 #define CHECK(x)                                                    \
   do {                                                              \
