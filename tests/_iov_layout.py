@@ -94,7 +94,12 @@ def gaps_intact(arena, segs):
 # vector path a multi-tile segment that is its own input, segments with a
 # head and with a tail, and (8-byte elements, where 4097 elements past a head
 # still span two tiles) a multi-tile segment with a head
-TREE_SHIFT = {2: 1, 4: 3, 8: 39}
+TREE_SHIFT = {2: 1, 4: 3, 8: 39,
+              # tests/_sweep.py (assert_treev_paths): a 1-byte element is never
+              # misaligned and one tile holds 4097 of them; a 16-byte element
+              # is on the vector path only at offset 0, where shift 3 puts the
+              # 4097-element segment that is its own input
+              1: 1, 16: 3}
 
 
 def tree_layout(esz, nsrc):

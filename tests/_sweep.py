@@ -1,0 +1,465 @@
+"""The oracle sweep's cases and inputs: no GPU, no product code.
+
+tests/test_sweep_gpu.py runs every (op, datatype) pair through every tree,
+tree-put and list-form kernel instantiation liblfa.so holds;
+tests/test_sweep_cpu.py runs the same cases through the host combine and
+checks the conditions below on the inputs themselves.  This module builds the
+cases: the pair lists, operands whose result depends on EVERY input, the byte
+offsets that send a launcher down each of its paths, and one arena per case
+(64 sentinel bytes between operands, tests/_iov_layout.py's convention) from
+which every operand is carved, so a case is one upload and one download and a
+write outside any operand shows.
+
+Why not the random operands of the other tree tests: at wide fan-in they go
+blind.  BAND of 32 uniform integers is 0 on practically every lane, BOR all
+ones, integer PROD 0 mod 2^k, LAND / LOR constant, so a body that dropped or
+duplicated a leaf would still pass.  `inputs` below keeps every input
+visible in the result at 32 inputs (tests/test_sweep_cpu.py holds it to that).
+"""
+import numpy as np
+
+import oracle
+from tests import _half_ref as R
+from tests import _iov_layout as L
+from tests._cmp import assert_parity
+
+MIN, MAX, SUM, PROD, LOR, LAND, BOR, BAND, LXOR, BXOR, READ, WRITE = range(12)
+HALF = (R.FLOAT16, R.BFLOAT16)
+HALF_REDUCE_OPS = (MIN, MAX, SUM, PROD, LOR, LAND, LXOR)
+
+# What the sweep must cover.  Literals: the tests compare them with the lists
+# built below and with atomic.reduce_valid, so a pair that silently left a
+# list fails instead of shrinking the sweep.
+N_REDUCE_PAIRS = 133        # 119 table entries (ops 0..9) + 2 half types x 7 ops
+N_WRITE_PAIRS = 148         # the 132 golden combine entries + 2 half types x 8 ops
+
+TREE_NSRC = (2, 3, 5, 8, 9, 17, 32)
+PUT_NSRC = (1, 3, 5, 9, 17, 32)
+PUT_NDST = (2, 6)
+# 2 and 3 inputs: reduce_iov's 2-leaf body; 5: the 4-leaf one; 8 and 15: 8 leaves
+TREEV_NSRC = (2, 3, 5, 8, 15)
+TREE_ALIAS = ("highest", "input0")
+PATHS = ("vec", "head", "elem", "bytes")
+# paths a launcher can take per element size: a 1-byte element is never
+# misaligned; a 16-byte element that is aligned is co-aligned
+N_PATHS = {1: 3, 2: 4, 4: 4, 8: 4, 16: 2}
+
+OUT_FILL = 0x3C             # an output before the call (neither sentinel nor 0)
+
+
+def np_dtype(dt: int) -> np.dtype:
+    return np.dtype(np.uint16) if dt in HALF else oracle.DT_NP[dt]
+
+
+def esz_of(dt: int) -> int:
+    return np_dtype(dt).itemsize
+
+
+def reduce_pairs():
+    """(op, dt) of every reducing instantiation, op-major."""
+    table = [(op, dt) for op in range(10) for dt in oracle.DT_NP if oracle.has_handler(op, dt)]
+    half = [(op, dt) for op in HALF_REDUCE_OPS for dt in HALF]
+    return sorted(table + half)
+
+
+def write_pairs(manifest):
+    """(op, dt) of every binary list-form instantiation: the golden manifest's
+    combine entries plus the half types' write rows."""
+    table = [(c["op"], c["dt"]) for c in manifest["combine"]]
+    half = [(op, dt) for op in R.OPS for dt in HALF]
+    return sorted(table + half)
+
+
+def dts_of(op: int):
+    return [dt for o, dt in reduce_pairs() if o == op]
+
+
+def paths_of(esz: int):
+    return [p for p in PATHS
+            if not (p in ("head", "elem") and esz >= 16) and not (p == "bytes" and esz == 1)]
+
+
+# ------------------------------------------------------------- reference --
+
+def reference(op: int, dt: int, ins) -> np.ndarray:
+    """prov/coll's tree over `ins` (byte arrays), as bytes."""
+    if dt in HALF:
+        return R.tree(dt, op, [np.ascontiguousarray(x).view(np.uint16) for x in ins]).view(np.uint8)
+    nd = oracle.DT_NP[dt]
+    return oracle.allreduce(op, dt, [np.ascontiguousarray(x).view(nd).copy()
+                                     for x in ins])[0].view(np.uint8)
+
+
+def reference_write(op: int, dt: int, dst, src) -> np.ndarray:
+    """dst OP src (byte arrays), as bytes."""
+    if dt in HALF:
+        return R.step(dt, op, np.ascontiguousarray(dst).view(np.uint16),
+                      np.ascontiguousarray(src).view(np.uint16)).view(np.uint8)
+    nd = oracle.DT_NP[dt]
+    d = np.ascontiguousarray(dst).view(nd).copy()
+    if d.size:
+        oracle.write(op, dt, d, np.ascontiguousarray(src).view(nd).copy())
+    return d.view(np.uint8)
+
+
+def assert_same(dt: int, got, want, what: str) -> None:
+    if dt in HALF:
+        R.assert_half(dt, np.ascontiguousarray(got).view(np.uint16),
+                      np.ascontiguousarray(want).view(np.uint16), what)
+    else:
+        assert_parity(dt, got, want, what)
+
+
+def nan_lanes(dt: int, b) -> np.ndarray:
+    """Per element: is any component NaN (float, complex and half types)."""
+    b = np.ascontiguousarray(b)
+    if dt in HALF:
+        return R.isnan(dt, b.view(np.uint16))
+    nd = oracle.DT_NP[dt]
+    if nd.kind == "c":
+        v = b.view(nd)
+        return np.isnan(v.real) | np.isnan(v.imag)
+    return np.isnan(b.view(nd))
+
+
+def is_float(dt: int) -> bool:
+    return dt in HALF or oracle.DT_NP[dt].kind in "fc"
+
+
+# ---------------------------------------------------------------- inputs --
+
+EDGE_LANES = 64
+
+
+def _edges(dt: int):
+    """The edge values of dt, or None (int128): +-0, +-inf, NaN of either
+    sign, the smallest normal, +-smallest subnormal, +-largest finite and +-1
+    for the float types (every pair of them for complex, _half_ref.SPECIALS
+    for the half types); min, max, 0, 1, max - 1 and -1 for the integers."""
+    if dt in HALF:
+        return np.array(R.SPECIALS[dt], np.uint16)
+    nd = oracle.DT_NP[dt]
+    if nd.kind == "V":
+        return None
+    if nd.kind == "c":
+        f = _edges(oracle.DT_CODE["FLOAT"])
+        c = np.empty(f.size * f.size, nd)
+        c.real, c.imag = np.repeat(f, f.size), np.tile(f[::-1], f.size)
+        return c
+    if nd.kind == "f":
+        fi = np.finfo(nd)
+        return np.array([0.0, -0.0, np.inf, -np.inf, np.nan, -np.nan, fi.tiny,
+                         fi.smallest_subnormal, -fi.smallest_subnormal, fi.max, -fi.max,
+                         1.0, -1.0], dtype=nd)
+    ii = np.iinfo(nd)
+    return np.array([ii.min, ii.max, 0, 1, ii.max - 1] + ([-1] if ii.min < 0 else []), dtype=nd)
+
+
+def _floats(dt: int, f: np.ndarray) -> np.ndarray:
+    """float64 values -> (n, esz) bytes of dt (complex: pairs of values)."""
+    if dt in HALF:
+        x = R.from_float(dt, f)
+    else:
+        nd = oracle.DT_NP[dt]
+        x = f.astype(np.float32).view(np.complex64) if nd.kind == "c" else f.astype(nd)
+    return x.view(np.uint8).reshape(-1, esz_of(dt)).copy()
+
+
+def inputs(op: int, dt: int, nsrc: int, n: int, rng) -> list:
+    """nsrc operands of n elements (byte arrays) whose result under `op`
+    depends on every one of them.
+
+    SUM, float / complex PROD: magnitudes 0.5..1.5 with a random sign;
+    integers uniform.  Integer PROD: odd factors, so the wrapped product
+    keeps every bit.  MIN / MAX: uniform, and for the float types every input
+    holds +0 or -0 on a tenth of the lanes (the result there is decided by
+    the association order alone).  BAND: all ones, except that per lane one
+    input holds a random mask; BOR the mirror image over zeros.  LAND: every
+    input nonzero, except that on half the lanes one input is zero; LOR the
+    mirror image.  LXOR: each lane zero with probability 1/2; BXOR uniform.
+    ATOMIC_WRITE takes SUM's.  The last 64 lanes of every input hold edge
+    values (NaN, +-inf, subnormals, type extremes), so the bulk stays finite.
+    """
+    esz = esz_of(dt)
+    flt = is_float(dt)
+    comp = 2 if (dt not in HALF and oracle.DT_NP[dt].kind == "c") else 1
+    xs = []
+    for _ in range(nsrc):
+        if flt and op in (MIN, MAX):
+            x = _floats(dt, rng.uniform(-2.0, 2.0, n * comp))
+        elif flt:
+            x = _floats(dt, rng.uniform(0.5, 1.5, n * comp) * rng.choice([-1.0, 1.0], n * comp))
+        else:
+            x = rng.integers(0, 256, (n, esz), dtype=np.uint8)      # uniform over the type
+        xs.append(x)
+    who = rng.integers(0, nsrc, n)          # per lane: the input that differs
+    half = rng.random(n) < 0.5
+    if op == PROD and not flt:
+        for x in xs:
+            x[:, 0] |= 1
+    elif op in (MIN, MAX) and flt:
+        zero = rng.random(n) < 0.1
+        for x in xs:
+            x[zero] = 0
+            if dt in HALF:      # the sign bit of random 16-bit patterns
+                sign = (R.patterns(n, int(rng.integers(0, 2**31))) >> 8).astype(np.uint8) & 0x80
+            else:
+                sign = rng.choice(np.array([0, 0x80], np.uint8), n)
+            x[zero, esz - 1] = sign[zero]
+    elif op in (BAND, BOR):
+        mask = rng.integers(0, 256, (n, esz), dtype=np.uint8)
+        rest = 0xFF if op == BAND else 0
+        for k, x in enumerate(xs):
+            x[:] = np.where((who == k)[:, None], mask, np.uint8(rest))
+    elif op in (LAND, LOR):
+        for k, x in enumerate(xs):
+            if not flt:
+                x[:, 0] |= 1                # nonzero
+            odd = (who == k) & half         # the lane's one zero (LAND) / nonzero (LOR)
+            x[odd if op == LAND else ~odd] = 0
+    elif op == LXOR:
+        for x in xs:
+            if not flt:
+                x[:, 0] |= 1
+            x[rng.random(n) < 0.5] = 0
+    ev = _edges(dt)
+    ne = min(EDGE_LANES, n)
+    if ev is not None and ne:
+        eb = np.ascontiguousarray(ev).view(np.uint8).reshape(-1, esz)
+        for x in xs:
+            x[n - ne:] = eb[rng.integers(0, eb.shape[0], ne)]
+    return [x.reshape(-1) for x in xs]
+
+
+# ---------------------------------------------------------------- layout --
+
+def lanes(esz: int) -> int:
+    """The smallest count that gives the widest body (16 KiB of output per
+    workgroup: reduce_tree_put with U = 4, combine_iov) two whole workgroup
+    tiles, a partial tile, a partial wave and a ragged tail."""
+    return (40 * 1024 + 16 * 37) // esz + 3
+
+
+def layout(esz: int, path: str, ndst: int = 1, nsrc: int = 2):
+    """(n, output offsets, input offsets): where each operand starts, in bytes
+    past a 16-byte boundary, for a launcher to take `path`.
+
+    vec    every operand 16-byte aligned: vector body, a partial wave, a tail
+    head   every operand esz bytes past a boundary, co-aligned: the tree takes
+           the element kernel for the whole buffer, the put form peels a head
+    elem   input 1 one element further on than the rest (with one input: the
+           last output): element path
+    bytes  output 0 and input 0 one byte off: bytes path
+    """
+    assert path in paths_of(esz), (esz, path)
+    outs, ins = [0] * ndst, [0] * nsrc
+    if path == "head":
+        outs, ins = [esz] * ndst, [esz] * nsrc
+    elif path == "elem":
+        if nsrc > 1:
+            ins[1] = esz
+        else:
+            assert ndst > 1
+            outs[-1] = esz
+    elif path == "bytes":
+        outs[0] = ins[0] = 1
+    return lanes(esz), outs, ins
+
+
+def expect_path(esz: int, outs, ins) -> str:
+    """lfa_split.h's rule on the offsets: which path a launcher takes."""
+    offs = list(outs) + list(ins)
+    if any(o % esz for o in offs):
+        return "bytes"
+    if any((o - outs[0]) % 16 for o in offs) or esz > 16:
+        return "elem"
+    return "head" if outs[0] % 16 else "vec"
+
+
+class Case:
+    """One call's operands in one arena.  `outs` / `ins`: (start, bytes) per
+    operand; an aliased output is the same range as its input.  `want`: the
+    bytes every output must hold afterwards."""
+
+    def __init__(self, arena, outs, ins, want, what, segs):
+        self.arena, self.outs, self.ins = arena, outs, ins
+        self.want, self.what, self.segs = want, what, segs
+
+    def check(self, dt: int, got: np.ndarray) -> None:
+        got = np.asarray(got)
+        assert got.shape == self.arena.shape, self.what
+        assert L.gaps_intact(got, self.segs), f"{self.what}: a gap lost its sentinel"
+        for k, (lo, nb) in enumerate(self.ins):
+            if (lo, nb) not in self.outs:
+                assert np.array_equal(got[lo:lo + nb], self.arena[lo:lo + nb]), \
+                    f"{self.what}: input {k} changed"
+        for j, (lo, nb) in enumerate(self.outs):
+            assert_same(dt, got[lo:lo + nb].copy(), self.want, f"{self.what} out {j}")
+
+
+def carve(dt, data, want, path, ndst=1, alias=None, what=""):
+    """A Case for the operands `data` on `path` with ndst outputs; alias:
+    None, "highest" or "input0": the one output IS that input."""
+    esz, nsrc = esz_of(dt), len(data)
+    n, o_off, i_off = layout(esz, path, 0 if alias else ndst, nsrc)
+    assert n * esz == data[0].size
+    assert expect_path(esz, o_off or [i_off[-1 if alias == "highest" else 0]], i_off) == path
+    segs, size = L.plan([n] * (len(o_off) + nsrc), o_off + i_off, esz)
+    arena = np.full(size, L.SENTINEL, np.uint8)
+    outs, ins = segs[:len(o_off)], segs[len(o_off):]
+    for lo, nb in outs:
+        arena[lo:lo + nb] = OUT_FILL
+    for (lo, nb), x in zip(ins, data):
+        arena[lo:lo + nb] = x
+    if alias:
+        outs = [ins[-1 if alias == "highest" else 0]]
+    return Case(arena, outs, ins, want, what, segs)
+
+
+def tree_cases(op, dt, rng, nsrcs=TREE_NSRC):
+    """Every case of the single-call tree for one pair: each fan-in on each
+    path, and on the vec path once more with the output aliasing the highest
+    input and once with it aliasing input 0."""
+    esz = esz_of(dt)
+    for nsrc in nsrcs:
+        data = inputs(op, dt, nsrc, lanes(esz), rng)
+        want = reference(op, dt, data)
+        for path in paths_of(esz):
+            yield carve(dt, data, want, path, what=f"tree op={op} dt={dt} nsrc={nsrc} {path}")
+        for alias in TREE_ALIAS:
+            yield carve(dt, data, want, "vec", alias=alias,
+                        what=f"tree op={op} dt={dt} nsrc={nsrc} out is {alias}")
+
+
+def n_tree_cases(op) -> int:
+    return sum(len(TREE_NSRC) * (N_PATHS[esz_of(dt)] + len(TREE_ALIAS)) for dt in dts_of(op))
+
+
+def put_cases(op, dt, rng):
+    """(ndst, Case) of the tree-put form for one pair."""
+    esz = esz_of(dt)
+    for nsrc in PUT_NSRC:
+        data = inputs(op, dt, nsrc, lanes(esz), rng)
+        want = reference(op, dt, data)
+        for path in paths_of(esz):
+            for ndst in PUT_NDST:
+                yield carve(dt, data, want, path, ndst=ndst,
+                            what=f"put op={op} dt={dt} nsrc={nsrc} ndst={ndst} {path}")
+
+
+def n_put_cases(op) -> int:
+    return sum(len(PUT_NSRC) * N_PATHS[esz_of(dt)] * len(PUT_NDST) for dt in dts_of(op))
+
+
+# ------------------------------------------------------------ list forms --
+
+class ListCase:
+    """A list-form call: every arena of the call back to back in ONE buffer
+    (`arena`), each from a 256-byte boundary.  dst[i] / src[k][i]: (start,
+    bytes) in that buffer; want[i]: segment i's bytes afterwards."""
+
+    def __init__(self, arena, dst, src, want, what):
+        self.arena, self.dst, self.src = arena, dst, src
+        self.want, self.what = want, what
+
+    def check(self, dt: int, got: np.ndarray) -> None:
+        got = np.asarray(got)
+        keep = np.ones(got.size, bool)
+        for lo, nb in self.dst:
+            keep[lo:lo + nb] = False
+        # every gap, every input and every input arena's unused bytes
+        assert np.array_equal(got[keep], self.arena[keep]), \
+            f"{self.what}: bytes outside the dst segments changed"
+        for i, (lo, nb) in enumerate(self.dst):
+            assert_same(dt, got[lo:lo + nb].copy(), self.want[i], f"{self.what} seg {i}")
+
+
+def _pack(arenas):
+    """Arenas back to back from 256-byte boundaries: the buffer, each base."""
+    bases, pos = [], 0
+    for a in arenas:
+        bases.append(pos)
+        pos += (a.size + 255) // 256 * 256
+    big = np.full(pos, L.SENTINEL, np.uint8)
+    for b, a in zip(bases, arenas):
+        big[b:b + a.size] = a
+    return big, bases
+
+
+def _split(x, counts, esz):
+    cuts = np.cumsum([0] + [c * esz for c in counts])
+    return [x[cuts[i]:cuts[i + 1]] for i in range(len(counts))]
+
+
+def writev_kinds(esz):
+    return {"vector", "element", "bytes"} - {"bytes" if esz == 1 else "",
+                                             "element" if esz == 16 else ""}
+
+
+def writev_case(op, dt, rng):
+    """37 segments (_iov_layout.standard): vector, element and bytes segments
+    in one call; every third source starts where the next segment's dst does."""
+    esz, nseg = esz_of(dt), 37
+    counts, offsets, (segs, size) = L.standard(nseg, esz, shift=op)
+    soffs = [offsets[(i + 1) % nseg] if i % 3 == 2 else o for i, o in enumerate(offsets)]
+    ssegs, ssize = L.plan(counts, soffs, esz)
+    kinds = {p[0] for p in (L.path(esz, c, o, [so])
+                            for c, o, so in zip(counts, offsets, soffs)) if p}
+    assert kinds == writev_kinds(esz), (esz, kinds)
+    d, s = inputs(SUM if op == WRITE else op, dt, 2, sum(counts), rng)
+    da, sa = np.full(size, L.SENTINEL, np.uint8), np.full(ssize, L.SENTINEL, np.uint8)
+    want = []
+    for (lo, nb), (slo, _), dseg, sseg in zip(segs, ssegs, _split(d, counts, esz),
+                                              _split(s, counts, esz)):
+        da[lo:lo + nb], sa[slo:slo + nb] = dseg, sseg
+        want.append(reference_write(op, dt, dseg, sseg))
+    big, (db, sb) = _pack([da, sa])
+    return ListCase(big, [(db + lo, nb) for lo, nb in segs], [[(sb + lo, nb) for lo, nb in ssegs]],
+                    want, f"writev op={op} dt={dt}")
+
+
+def assert_treev_paths(esz, paths):
+    """tree_layout()'s segments reach every path the element size has, each
+    with aliased and unaliased segments (_iov_layout.assert_tree_paths is the
+    full statement for the sizes that have all three)."""
+    if esz in (2, 4, 8):
+        L.assert_tree_paths(esz, paths)
+        return
+    paths = [(p, own) for p, own in paths if p]
+    for kind in ("vector", "element", "bytes"):
+        owns = {own for p, own in paths if p[0] == kind}
+        assert owns == ({True, False} if kind in writev_kinds(esz) else set()), (esz, kind)
+    vec = [(head, tail, tiles, own) for (kind, head, tail, tiles), own in paths
+           if kind == "vector"]
+    if esz == 1:
+        assert any(head for head, *_ in vec) and any(tail for _, tail, *_ in vec)
+    else:       # 4097 sixteen-byte elements: four tiles and a fifth, partial one
+        assert any(tiles > 1 and own for *_, tiles, own in vec)
+
+
+def treev_case(op, dt, nsrc, rng):
+    """_iov_layout.tree_layout's 19 segments; dst[i] is its own input 0 for
+    even i."""
+    esz = esz_of(dt)
+    segs, size, in_k, paths = L.tree_layout(esz, nsrc)
+    assert_treev_paths(esz, paths)
+    counts = [nb // esz for _, nb in segs]
+    data = [_split(x, counts, esz) for x in inputs(op, dt, nsrc, sum(counts), rng)]
+    nseg = len(segs)
+    da = np.full(size, L.SENTINEL, np.uint8)
+    for i, (lo, nb) in enumerate(segs):
+        da[lo:lo + nb] = data[0][i] if i % 2 == 0 else OUT_FILL
+    arenas = [da]
+    for k, (sk, size_k) in enumerate(in_k):
+        a = np.full(size_k, L.SENTINEL, np.uint8)
+        for i, (lo, nb) in enumerate(sk):
+            a[lo:lo + nb] = data[k][i]
+        arenas.append(a)
+    big, bases = _pack(arenas)
+    dst = [(bases[0] + lo, nb) for lo, nb in segs]
+    src = [[(bases[1 + k] + lo, nb) for lo, nb in in_k[k][0]] for k in range(nsrc)]
+    for i in range(0, nseg, 2):
+        src[0][i] = dst[i]
+    want = [reference(op, dt, [data[k][i] for k in range(nsrc)]) if counts[i]
+            else np.zeros(0, np.uint8) for i in range(nseg)]
+    return ListCase(big, dst, src, want, f"treev op={op} dt={dt} nsrc={nsrc}")

@@ -333,7 +333,10 @@ def test_gpu_write_any_shape(pair, n, doff, soff, edge, seed):
        seed=st.integers(0, 2**31))
 def test_gpu_tree_any_fan_in(pair, nsrc, n, off, edge, seed):
     """lfa_reduce_tree_async: any fan-in (the 2/4/8/16/32-leaf bodies and
-    their pair leaves), any length, inputs at a drawn common offset."""
+    their pair leaves), any length, inputs at a drawn common offset.  Wide
+    fan-ins of BAND / BOR / LAND / LOR / integer PROD are tests/test_sweep_gpu.py's
+    to check: over these uniform operands their results are constant (0, all
+    ones, 0 mod 2^k), so a dropped or duplicated leaf would not show here."""
     import torch
     from libfabric_amd import atomic
     op, dt = pair
