@@ -493,6 +493,16 @@ int lfa_coll_plan(enum lfa_collective_op coll, enum lfa_coll_algo algo,
 /* Block [off, off + len) of rank r when `count` splits over `nranks`. */
 void lfa_coll_block(size_t count, int nranks, int r, size_t *off, size_t *len);
 
+/* Bytes member `rank` of `nranks` reads from buf and writes to result for one
+ * collective of `count` elements of `esz` bytes: count·esz each, but
+ * reduce_scatter writes the member's block (lfa_coll_block), reduce writes
+ * nothing off the root, allgather writes nranks·count·esz, and scatter reads
+ * nranks·count·esz at the root and nothing elsewhere.  `root` is read for
+ * reduce and scatter only.  Pure. */
+void lfa_coll_io_bytes(enum lfa_collective_op coll, size_t count, int nranks,
+		       int rank, int root, size_t esz, size_t *in_bytes,
+		       size_t *out_bytes);
+
 /*
  * Host-buffer staging plan: chunk `idx` of a collective of `count` elements
  * of `esz` bytes over `nranks`, staged `chunk_bytes` at a time (the geometry

@@ -4,6 +4,7 @@ The provider is C; this module only marshals arguments:
 
   plan(...)        lfa_coll_plan — a rank's schedule as data (host only)
   block(...)       lfa_coll_block — reduce_scatter block bounds
+  io_bytes(...)    lfa_coll_io_bytes — bytes a member reads and writes
   host_chunks(...) lfa_coll_host_chunk — host-buffer staging geometry
   loopback(...)    lfa_coll_loopback — all ranks' schedules on ONE GPU
   Endpoint         domain + endpoint over RCCL; fi_ops_collective calls
@@ -95,6 +96,9 @@ def lib() -> ctypes.CDLL:
                                       c_size_t, P(HostChunk)]
     L.lfa_coll_block.restype = None
     L.lfa_coll_block.argtypes = [c_size_t, c_int, c_int, P(c_size_t), P(c_size_t)]
+    L.lfa_coll_io_bytes.restype = None
+    L.lfa_coll_io_bytes.argtypes = [c_int, c_size_t, c_int, c_int, c_int, c_size_t,
+                                    P(c_size_t), P(c_size_t)]
     L.lfa_coll_loopback.restype = c_int
     L.lfa_coll_loopback.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int,
                                     c_size_t, P(c_void_p), P(c_void_p), c_void_p]
@@ -323,6 +327,15 @@ def block(count: int, nranks: int, r: int) -> tuple[int, int]:
     off, ln = c_size_t(0), c_size_t(0)
     lib().lfa_coll_block(count, nranks, r, ctypes.byref(off), ctypes.byref(ln))
     return off.value, ln.value
+
+
+def io_bytes(coll: int, count: int, nranks: int, rank: int, root: int,
+             esz: int) -> tuple[int, int]:
+    """lfa_coll_io_bytes: the bytes a member reads from buf and writes to result."""
+    i, o = c_size_t(0), c_size_t(0)
+    lib().lfa_coll_io_bytes(coll, count, nranks, rank, root, esz, ctypes.byref(i),
+                            ctypes.byref(o))
+    return i.value, o.value
 
 
 def loopback(coll: int, algo: int, nranks: int, root: int, dt: int, op: int,

@@ -28,19 +28,12 @@
  * valid for every op including the bitwise/logical ones RCCL lacks.
  */
 #define _GNU_SOURCE
-#include <dirent.h>
-#include <errno.h>
 #include <pthread.h>
-#include <sched.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
-#include <unistd.h>
 
 #include "lfa_coll_int.h"
-
 
 int lfa_coll_get_unique_id(void *id, size_t len)
 {
@@ -275,7 +268,7 @@ int lfa_coll_ep_close(struct lfa_coll_ep *ep)
 		if (ep->q[(ep->qhead + i) % ep->qcap].ev)
 			hipEventDestroy(ep->q[(ep->qhead + i) % ep->qcap].ev);
 	for (size_t i = 0; i < ep->qlen; i++)
-		bounce_put(ep, ep->q[(ep->qhead + i) % ep->qcap].bounce);
+		bounce_put(ep, ep->q[(ep->qhead + i) % ep->qcap].bounce.block);
 	bounce_free_all(ep, drained);
 	for (int i = 0; i < ep->nev; i++)
 		hipEventDestroy(ep->evpool[i]);
@@ -410,338 +403,6 @@ static int grow(void **buf, size_t *size, size_t need, hipStream_t s)
 	*buf = nb;
 	*size = need;
 	return 0;
-}
-
-/* ---------------------------------------------------------------------- */
-/* completion queue                                                        */
-/* ---------------------------------------------------------------------- */
-
-LFA_INTERNAL void release_event(struct lfa_coll_ep *ep, hipEvent_t ev)
-{
-	if (ep->nev < (int)(sizeof(ep->evpool) / sizeof(ep->evpool[0])))
-		ep->evpool[ep->nev++] = ev;
-	else
-		hipEventDestroy(ev);
-}
-
-/* A completion event from the endpoint's pool (ep->lock held): creating
- * one costs a runtime call per operation otherwise.  NULL on failure. */
-LFA_INTERNAL hipEvent_t event_get(struct lfa_coll_ep *ep)
-{
-	hipEvent_t ev;
-
-	if (ep->nev)
-		return ep->evpool[--ep->nev];
-	return hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess ? ev : NULL;
-}
-
-/* Room for `n` more operations in the FIFO of in-flight operations (the
- * ring doubles as needed): 0 or -LFA_ENOMEM. */
-LFA_INTERNAL int queue_reserve(struct lfa_coll_ep *ep, size_t n)
-{
-	size_t cap = ep->qcap;
-
-	while (cap - ep->qlen < n)
-		cap *= 2;
-	if (cap != ep->qcap) {
-		struct pending *nq = calloc(cap, sizeof(*nq));
-
-		if (!nq)
-			return -LFA_ENOMEM;
-		for (size_t i = 0; i < ep->qlen; i++)
-			nq[i] = ep->q[(ep->qhead + i) % ep->qcap];
-		free(ep->q);
-		ep->q = nq;
-		ep->qhead = 0;
-		ep->qcap = cap;
-	}
-	return 0;
-}
-
-/* A free slot at the tail of the FIFO of in-flight operations. */
-LFA_INTERNAL struct pending *queue_slot(struct lfa_coll_ep *ep)
-{
-	if (queue_reserve(ep, 1))
-		return NULL;
-	return &ep->q[(ep->qhead + ep->qlen) % ep->qcap];
-}
-
-LFA_INTERNAL int enqueue_completion(struct lfa_coll_ep *ep, hipStream_t s,
-			      void *context, int kind, struct lfa_coll_mc *mc,
-			      uint64_t done_val, const uint64_t *done_w)
-{
-	struct pending *p = queue_slot(ep);
-
-	if (!p)
-		return -LFA_ENOMEM;
-	memset(p, 0, sizeof(*p));
-	if (done_val) {
-		/* the one-shot kernel stores done_val into the completion word:
-		 * no event to record or query */
-		p->done_val = done_val;
-		p->done_w = done_w;
-		/* p->ww stays unarmed: its bound starts at the head of the queue */
-		if (ep->drop_words > 0) {
-			/* test knob: a value the word never reaches */
-			ep->drop_words--;
-			p->done_val |= 1ull << 62;
-		}
-		p->context = context;
-		p->kind = kind;
-		p->mc = mc;
-		ep->qlen++;
-		return 0;
-	}
-	if (ep->nev)
-		p->ev = ep->evpool[--ep->nev];
-	else if (hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) != hipSuccess)
-		return -LFA_EIO;
-	if (hipEventRecord(p->ev, s) != hipSuccess) {
-		release_event(ep, p->ev);
-		return -LFA_EIO;
-	}
-	p->context = context;
-	p->kind = kind;
-	p->mc = mc;
-	ep->qlen++;
-	return 0;
-}
-
-/* Completion state of a queued operation: 0 done, 1 pending, <0 / hip error
- * code (>0 in *perr) failed. */
-static int pending_state(const struct lfa_coll_ep *ep, struct pending *p,
-			 int *perr)
-{
-	if (p->hop) {
-		if (p->hop->err) {
-			/* the failing HIP call's code when there was one */
-			*perr = p->hop->r.hip_err ? p->hop->r.hip_err : -p->hop->err;
-			return -1;
-		}
-		return p->hop->done ? 0 : 1;
-	}
-	if (p->done_val) {
-		const uint64_t *w = p->done_w ? p->done_w : ep->done_word;
-
-		if (*(const volatile uint64_t *)w >= p->done_val)
-			return 0;
-		return word_overdue(ep, w, ep->stream, &p->ww, perr);
-	}
-	hipError_t e = hipEventQuery(p->ev);
-
-	if (e == hipErrorNotReady)
-		return 1;
-	if (e != hipSuccess) {
-		*perr = (int)e;
-		return -1;
-	}
-	return 0;
-}
-
-/* failed: the operation was reaped in error (a word timeout, a failed queue
- * or stream) — its kernel may still run later and read or write its bounce
- * block, so the block leaves the pool for good instead of going back to be
- * refilled by the next submit (done_word_free keeps owed words
- * the same way).  A hop's own free synchronises its stream first. */
-static void pending_release(struct lfa_coll_ep *ep, struct pending *p, int failed)
-{
-	if (p->hop)
-		hop_free(p->hop);
-	else if (p->ev)
-		release_event(ep, p->ev);
-	if (failed && !p->hop)
-		bounce_retire(ep, p->bounce);
-	else
-		bounce_put(ep, p->bounce);
-	p->hop = NULL;
-	p->ev = NULL;
-	p->bounce = NULL;
-}
-
-/* Reap completed operations in issue order. */
-static void progress(struct lfa_coll_ep *ep, struct lfa_cq_entry *out,
-		     size_t count, size_t *nout)
-{
-	*nout = 0;
-	if (ep->dom->host)
-		host_progress_all(ep);
-	while (ep->qlen && !ep->have_err) {
-		struct pending *p = &ep->q[ep->qhead];
-		int perr = 0, st = pending_state(ep, p, &perr);
-
-		if (st > 0)
-			break;
-		if (st == 0 && p2p_timed_out(p)) {
-			/* a flag barrier or one-shot wait of this operation, or of
-			 * an earlier one of its group, gave up waiting for a member
-			 * (lfa_signal.h): this one and every later P2P operation of
-			 * the group fail; the earlier ones completed normally */
-			if (p->pmc)
-				p->pmc->sig_failed = 1;
-			st = -1;
-			perr = ETIMEDOUT;
-		} else if (st < 0 && p->pmc) {
-			/* a P2P operation reaped as failed for another cause (its
-			 * word's bound, a failed queue or stream): its kernel may
-			 * still run and post into the workspace, so the group takes
-			 * no further P2P operation and its workspace goes to the
-			 * quarantine at close, as after a timed-out wait */
-			p->pmc->sig_failed = 1;
-		}
-		if (st == 0 && p->bounce_bytes) {
-			/* a bounced operation's result to the caller's buffer */
-			memcpy(p->bounce_user, p->bounce_out, p->bounce_bytes);
-			p->bounce_bytes = 0;
-		}
-		if (p->chain && p->chain == ep->failed_chain) {
-			/* a chunk of an operation whose error was already
-			 * reported: its outcome is that error, no second entry */
-		} else if (p->kind == 0 && st == 0 && *nout >= count) {
-			break;
-		} else if (st < 0) {
-			ep->err.op_context = p->context;
-			ep->err.flags = LFA_COLLECTIVE;
-			/* a word operation's own cause (ETIMEDOUT / EIO), else EIO
-			 * with the HIP code as prov_errno */
-			ep->err.err = p->hop || (p->done_val && (perr == ETIMEDOUT || perr == EIO))
-				      ? perr : LFA_EIO;
-			ep->err.prov_errno = perr;
-			ep->have_err = 1;
-			if (p->chain)
-				ep->failed_chain = p->chain;
-		} else if (p->kind == 1) {
-			join_finish(ep, p->mc);
-		} else if (p->kind == 2) {
-			/* join of a handle closed before it completed */
-		} else if (p->kind == 3) {
-			/* a chunk of a larger operation (peer_chunked): its last
-			 * chunk completes it */
-		} else {
-			struct lfa_cq_entry *c = &out[(*nout)++];
-
-			memset(c, 0, sizeof(*c));
-			c->op_context = p->context;
-			c->flags = LFA_COLLECTIVE;
-		}
-		if (st == 0 && p->done_val)
-			ep->word_ops++;
-		pending_release(ep, p, st < 0);
-		ep->qhead = (ep->qhead + 1) % ep->qcap;
-		ep->qlen--;
-	}
-	if (ep->stage_trim_due && !ep->qlen) {
-		stage_trim(ep, ep->stage_cap);
-		ep->stage_trim_due = 0;
-	}
-}
-
-ssize_t lfa_cq_read(struct lfa_coll_ep *ep, struct lfa_cq_entry *buf,
-		    size_t count)
-{
-	size_t n;
-	int have_err;
-	ncclResult_t async;
-
-	if (!ep || (!buf && count))
-		return -LFA_EINVAL;
-	pthread_mutex_lock(&ep->lock);
-	progress(ep, buf, count, &n);
-	if (!n && !ep->have_err && !ep->dom->host &&
-	    ncclCommGetAsyncError(ep->dom->comm, &async) == ncclSuccess &&
-	    async != ncclSuccess && async != ncclInProgress) {
-		ep->err.op_context = ep->qlen ? ep->q[ep->qhead].context : NULL;
-		ep->err.flags = LFA_COLLECTIVE;
-		ep->err.err = LFA_EIO;
-		ep->err.prov_errno = (int)async;
-		ep->have_err = 1;
-	}
-	have_err = ep->have_err;
-	pthread_mutex_unlock(&ep->lock);
-	if (n)
-		return (ssize_t)n;
-	return have_err ? -LFA_EIO : -LFA_EAGAIN;
-}
-
-ssize_t lfa_cq_readerr(struct lfa_coll_ep *ep, struct lfa_cq_err_entry *buf)
-{
-	ssize_t ret = -LFA_EAGAIN;
-
-	if (!ep || !buf)
-		return -LFA_EINVAL;
-	pthread_mutex_lock(&ep->lock);
-	if (ep->have_err) {
-		*buf = ep->err;
-		ep->have_err = 0;
-		ret = 1;
-	}
-	pthread_mutex_unlock(&ep->lock);
-	return ret;
-}
-
-ssize_t lfa_eq_read(struct lfa_coll_ep *ep, uint32_t *event,
-		    struct lfa_eq_entry *entry)
-{
-	struct lfa_cq_entry tmp[1];
-	size_t n;
-	ssize_t ret = -LFA_EAGAIN;
-
-	if (!ep || !event || !entry)
-		return -LFA_EINVAL;
-	pthread_mutex_lock(&ep->lock);
-	/* progress joins only up to the first collective completion */
-	while (ep->qlen && ep->q[ep->qhead].kind == 1 && !ep->have_err) {
-		int perr;
-
-		progress(ep, tmp, 0, &n);
-		if (ep->qlen && ep->q[ep->qhead].kind == 1 &&
-		    pending_state(ep, &ep->q[ep->qhead], &perr) > 0)
-			break;
-	}
-	if (ep->dom->host && !(ep->qlen && ep->q[ep->qhead].kind == 1))
-		host_progress_all(ep);
-	if (ep->eqn) {
-		*event = ep->eq[ep->eqh].event;
-		*entry = ep->eq[ep->eqh].entry;
-		ep->eqh = (ep->eqh + 1) % 64;
-		ep->eqn--;
-		ret = (ssize_t)sizeof(*entry);
-	}
-	pthread_mutex_unlock(&ep->lock);
-	return ret;
-}
-
-int lfa_coll_ep_flush(struct lfa_coll_ep *ep)
-{
-	if (!ep)
-		return -LFA_EINVAL;
-	if (ep->dom->host) {
-		/* drive the transfers until every queued operation finished */
-		for (;;) {
-			int busy = 0, err = 0;
-
-			pthread_mutex_lock(&ep->lock);
-			host_progress_all(ep);
-			for (size_t i = 0; i < ep->qlen; i++) {
-				struct hop *h = ep->q[(ep->qhead + i) % ep->qcap].hop;
-
-				if (h && h->err)
-					err = h->err;
-				else if (h && !h->done)
-					busy = 1;
-			}
-			if (!busy && !err)
-				stage_trim(ep, 0);
-			pthread_mutex_unlock(&ep->lock);
-			if (err)
-				return err;
-			if (!busy)
-				return 0;
-			sched_yield();
-		}
-	}
-	return hipStreamSynchronize(ep->stream) == hipSuccess &&
-	       hipStreamSynchronize(ep->copy_stream) == hipSuccess &&
-	       hipStreamSynchronize(ep->d2h_stream) == hipSuccess ? 0 : -LFA_EIO;
 }
 
 /*
@@ -901,23 +562,25 @@ static int cached_plan(struct lfa_coll_ep *ep, const struct plan **out,
 LFA_INTERNAL int run_device(struct lfa_coll_ep *ep, struct lfa_coll_mc *mc,
 		      enum lfa_collective_op coll, const void *buf, void *result,
 		      size_t count, int root, enum lfa_datatype dt,
-		      enum lfa_op op, hipStream_t s, enum lfa_coll_algo algo)
+		      enum lfa_op op, hipStream_t s, enum lfa_coll_algo algo,
+		      int direct, struct op_done *done)
 {
 	const struct plan *pl;
 	size_t esz = lfa_reduce_datatype_size(dt);
 	const enum lfa_coll_algo asked = algo;
+	struct op_done unused;
 	struct xctx x;
 	int ret;
 
-	ep->op_done_val = 0;
-	ep->op_done_w = NULL;
+	if (!done)
+		done = &unused;
+	*done = (struct op_done){ 0, NULL };
 	if (algo == LFA_ALGO_RCCL && mc->size > 1 &&
 	    try_rccl(mc, coll, buf, result, count, root, dt, op, s, &ret))
 		return ret;
 	if (mc->size == 1 && s == ep->stream && ep->done_word &&
-	    (coll == LFA_ALLREDUCE || coll == LFA_REDUCE || coll == LFA_REDUCE_SCATTER) &&
-	    count * esz <= ep->solo_max)
-		return run_solo(ep, buf, result, count, dt);
+	    coll_reduces(coll) && count * esz <= ep->solo_max)
+		return run_solo(ep, buf, result, count, dt, direct, done);
 	if (algo == LFA_ALGO_AUTO)
 		algo = (enum lfa_coll_algo)lfa_coll_auto_algo(coll, count, mc->size, esz,
 							       mc->p2p_state >= 0);
@@ -964,7 +627,7 @@ replan:
 		ret = exec_plan(mc, pl, &x, op, dt, s);
 	}
 	if (!ret)
-		ep->op_done_val = x.done_val;
+		done->val = x.done_val;
 	return ret;
 }
 
@@ -999,10 +662,12 @@ static ssize_t submit(struct lfa_coll_ep *ep, enum lfa_collective_op coll,
 {
 	struct lfa_coll_mc *mc;
 	size_t esz, chunk;
-	uint64_t t0, done_val = 0;
-	const uint64_t *done_w = NULL;
-	int root = -1, ret, host, chunkable, zc1 = 0;
-	void *zb = NULL, *zr = NULL, *bnc = NULL;
+	struct op_done done = { 0, NULL };
+	struct bounce bnc = { NULL, NULL, NULL, 0 };
+	struct pending *p = NULL;
+	uint64_t t0;
+	int root = -1, ret, host, chunkable;
+	void *zb = NULL, *zr = NULL;
 
 	if (!ep)
 		return -LFA_EINVAL;
@@ -1017,8 +682,7 @@ static ssize_t submit(struct lfa_coll_ep *ep, enum lfa_collective_op coll,
 		if (root < 0)
 			return -LFA_EINVAL;
 	}
-	if (coll == LFA_ALLREDUCE || coll == LFA_REDUCE ||
-	    coll == LFA_REDUCE_SCATTER) {
+	if (coll_reduces(coll)) {
 		ret = check_reduce_args(dt, op);
 		if (ret)
 			return ret;
@@ -1030,24 +694,24 @@ static ssize_t submit(struct lfa_coll_ep *ep, enum lfa_collective_op coll,
 		const void *out = coll == LFA_REDUCE && mc->rank != root ? NULL : result;
 		int din = ep->dom->device >= 0 && in && count && is_device_ptr(in);
 		int dout = ep->dom->device >= 0 && out && count && is_device_ptr(out);
-		int dev = din || dout;
+		enum placement where = din || dout ? PLACE_DEVICE : PLACE_HOST;
 
-		if (dev && ((in && count && !din) || (out && count && !dout)))
+		if (where == PLACE_DEVICE &&
+		    ((in && count && !din) || (out && count && !dout)))
 			return -LFA_EINVAL;
 		/* LFA_ALGO_P2P on a GPU peer domain: host buffers follow the
 		 * device schedule too (staged), so members may still mix */
-		if (!dev && ep->dom->device >= 0 && ep->algo == LFA_ALGO_P2P && count &&
-		    mc->size > 1 && mc->size <= LFA_TREE_MAX && mc->size <= LFA_PUT_MAX &&
-		    (coll == LFA_ALLREDUCE || coll == LFA_REDUCE_SCATTER ||
-		     coll == LFA_REDUCE))
-			dev = 2;
+		if (where == PLACE_HOST && ep->dom->device >= 0 &&
+		    ep->algo == LFA_ALGO_P2P && count && mc->size > 1 &&
+		    mc->size <= LFA_TREE_MAX && mc->size <= LFA_PUT_MAX && coll_reduces(coll))
+			where = PLACE_HOST_DEV;
 		pthread_mutex_lock(&ep->lock);
-		if (dev && (chunk = peer_chunked(ep, mc, coll, count, esz)))
+		if (where != PLACE_HOST && (chunk = peer_chunked(ep, mc, coll, count, esz)))
 			ret = peer_submit_chunked(ep, mc, coll, buf, result, count, root, dt,
-						  op, context, dev, chunk);
+						  op, context, where, chunk);
 		else
 			ret = host_submit(ep, mc, coll, buf, result, count, root, dt, op,
-					  context, 0, NULL, dev, ep->algo);
+					  context, PEND_COLL, NULL, where, ep->algo, 0);
 		pthread_mutex_unlock(&ep->lock);
 		return ret;
 	}
@@ -1068,24 +732,15 @@ static ssize_t submit(struct lfa_coll_ep *ep, enum lfa_collective_op coll,
 				      lfa_coll_group_chunk(ep->group_chunk, mc->size,
 							   count * esz),
 				      ep->chunk);
-	if (count && host && mc->size == 1 &&
-	    (coll == LFA_ALLREDUCE || coll == LFA_REDUCE || coll == LFA_REDUCE_SCATTER)) {
+	if (count && host && mc->size == 1 && coll_reduces(coll)) {
+		/* both operands mapped (pinned buffers, or a bounce block for
+		 * pageable ones), or neither: staged */
 		zb = zero_copy_of(buf, ep->dom->device);
 		zr = zero_copy_of(result, ep->dom->device);
-		if (zb && zr) {
-			zc1 = 1;
-		} else if (count * esz <= LFA_BOUNCE_BYTES && buf && result && !is_device_ptr(buf) &&
-			   !is_device_ptr(result) && (bnc = bounce_get(ep))) {
-			zb = zero_copy_of(bnc, ep->dom->device);
-			zr = zero_copy_of((char *)bnc + LFA_BOUNCE_BYTES, ep->dom->device);
-			if (zb && zr) {
-				memcpy(bnc, buf, count * esz);
-				zc1 = 2;
-			} else {
-				bounce_put(ep, bnc);
-				bnc = NULL;
-			}
-		}
+		if ((!zb || !zr) &&
+		    (!buf || !result || is_device_ptr(buf) || is_device_ptr(result) ||
+		     bounce_acquire(ep, &bnc, mc, coll, buf, result, count, root, esz, &zb, &zr)))
+			zb = zr = NULL;
 	}
 	if (!count) {
 		ret = 0;
@@ -1095,26 +750,16 @@ static ssize_t submit(struct lfa_coll_ep *ep, enum lfa_collective_op coll,
 					 chunk);
 	} else if (!host) {
 		/* a small bucket's one-shot kernel ends in the completion word */
-		ep->op_done_val = 0;
-		ep->op_done_w = NULL;
-		ep->allow_direct = 1;
 		ret = run_device(ep, mc, coll, buf, result, count, root, dt, op,
-				 ep->stream, ep->algo);
-		ep->allow_direct = 0;
-		done_val = ep->op_done_val;
-		done_w = ep->op_done_w;
-	} else if (zc1) {
+				 ep->stream, ep->algo, 1, &done);
+	} else if (zb) {
 		/* a one-member group's reducing collective is a copy; with
 		 * pinned host buffers it runs on their mappings over PCIe, no
 		 * staging (32 MiB 1.35 -> 0.93 ms);
 		 * pageable ones of at most LFA_BOUNCE_BYTES through a pinned
 		 * bounce block (copied in here, out when reaped) */
 		if (count * esz <= ep->solo_max) {
-			ep->op_done_val = 0;
-			ep->op_done_w = NULL;
-			ret = run_solo(ep, zb, zr, count, dt);
-			done_val = ep->op_done_val;
-			done_w = ep->op_done_w;
+			ret = run_solo(ep, zb, zr, count, dt, 0, &done);
 		} else {
 			ret = lfa_atomic_write_async(LFA_ATOMIC_WRITE, LFA_UINT8, zr, zb,
 						     count * esz, ep->stream);
@@ -1123,36 +768,18 @@ static ssize_t submit(struct lfa_coll_ep *ep, enum lfa_collective_op coll,
 		ret = run_host_chunked(ep, mc, coll, buf, result, count, root, dt,
 				       op, chunk);
 	} else {
-		size_t moff, mlen, in_b = count * esz, out_b = count * esz;
-
-		lfa_coll_block(count, mc->size, mc->rank, &moff, &mlen);
-		if (coll == LFA_REDUCE_SCATTER)
-			out_b = mlen * esz;
-		else if (coll == LFA_ALLGATHER)
-			out_b = (size_t)mc->size * count * esz;
-		else if (coll == LFA_SCATTER)
-			in_b = mc->rank == root ? (size_t)mc->size * count * esz : 0;
-		else if (coll == LFA_REDUCE && mc->rank != root)
-			out_b = 0;
-		ret = run_host_whole(ep, mc, coll, buf, in_b, result, out_b, count,
-				     root, dt, op);
+		ret = run_host_whole(ep, mc, coll, buf, result, count, root, dt, op);
 	}
 	if (!ret)
-		ret = enqueue_completion(ep, ep->stream, context, 0, NULL, done_val, done_w);
-	if (!ret && bnc) {
-		struct pending *p = &ep->q[(ep->qhead + ep->qlen - 1) % ep->qcap];
-
+		p = enqueue_completion(ep, ep->stream, context, PEND_COLL, NULL, done, &ret);
+	if (p) {
 		p->bounce = bnc;
-		p->bounce_out = (char *)bnc + LFA_BOUNCE_BYTES;
-		p->bounce_user = result;
-		p->bounce_bytes = count * esz;   /* one member: its block is everything */
-	} else if (bnc) {
+		tag_p2p(p, mc, t0);
+	} else if (bnc.block) {
 		/* the copy may be on the stream: wait before reusing the block */
 		hipStreamSynchronize(ep->stream);
-		bounce_put(ep, bnc);
+		bounce_put(ep, bnc.block);
 	}
-	if (!ret)
-		tag_p2p(ep, mc, t0);
 	pthread_mutex_unlock(&ep->lock);
 	return ret;
 }
@@ -1237,6 +864,8 @@ ssize_t lfa_barrier(struct lfa_coll_ep *ep, lfa_addr_t coll_addr, void *context)
 	/* coll_ep_barrier2 (coll_coll.c:997-1033): an allreduce of ~rank with
 	 * FI_BAND over one uint64. */
 	struct lfa_coll_mc *mc;
+	struct op_done done = { 0, NULL };
+	struct pending *p = NULL;
 	uint64_t t0;
 	int ret;
 
@@ -1254,9 +883,10 @@ ssize_t lfa_barrier(struct lfa_coll_ep *ep, lfa_addr_t coll_addr, void *context)
 			h->scratch[0] = ~(uint64_t)mc->rank;
 			mc->seq++;
 			ret = host_start(ep, h, mc, LFA_ALLREDUCE, &h->scratch[0],
-					 &h->scratch[1], 1, -1, LFA_UINT64, LFA_BAND, 0, ep->algo);
+					 &h->scratch[1], 1, -1, LFA_UINT64, LFA_BAND,
+					 PLACE_HOST, ep->algo);
 			if (!ret)
-				ret = enqueue_host(ep, h, context, 0, NULL);
+				enqueue_host(ep, h, context, PEND_COLL, NULL, &ret);
 			if (ret)
 				hop_free(h);
 		}
@@ -1265,20 +895,19 @@ ssize_t lfa_barrier(struct lfa_coll_ep *ep, lfa_addr_t coll_addr, void *context)
 	}
 	hipSetDevice(ep->dom->device);
 	t0 = mc->p2p_ticket;
-	ep->op_done_val = 0;
 	ep->barrier_host[0] = ~(uint64_t)mc->rank;
 	ret = hipMemcpyAsync(ep->barrier_dev, ep->barrier_host, sizeof(uint64_t),
 			     hipMemcpyHostToDevice, ep->stream) == hipSuccess ?
 	      0 : -LFA_EIO;
+	/* never direct: the staging copy above is stream-ordered */
 	if (!ret)
 		ret = run_device(ep, mc, LFA_ALLREDUCE, ep->barrier_dev,
 				 (uint64_t *)ep->barrier_dev + 1, 1, -1, LFA_UINT64,
-				 LFA_BAND, ep->stream, ep->algo);
+				 LFA_BAND, ep->stream, ep->algo, 0, &done);
 	if (!ret)
-		ret = enqueue_completion(ep, ep->stream, context, 0, NULL, ep->op_done_val,
-					 ep->op_done_w);
-	if (!ret)
-		tag_p2p(ep, mc, t0);
+		p = enqueue_completion(ep, ep->stream, context, PEND_COLL, NULL, done, &ret);
+	if (p)
+		tag_p2p(p, mc, t0);
 	pthread_mutex_unlock(&ep->lock);
 	return ret;
 }

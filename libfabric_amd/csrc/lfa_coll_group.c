@@ -265,11 +265,12 @@ static int join_impl(struct lfa_coll_ep *ep, lfa_addr_t coll_addr,
 			ret = host_submit(ep, members_only ? mc : parent, LFA_ALLREDUCE,
 					  mc->mask_host + LFA_CID_BYTES, mc->mask_host,
 					  LFA_CID_BYTES, -1, LFA_UINT8, LFA_BAND,
-					  context, 1, mc, 0, LFA_ALGO_TREE);
+					  context, PEND_JOIN, mc, PLACE_HOST, LFA_ALGO_TREE, 0);
 		}
 	} else if (!ret) {
 		struct lfa_coll_mc *over = members_only ? mc : parent;
 		const uint64_t t0 = over->p2p_ticket;
+		struct pending *p = NULL;
 
 		hipSetDevice(ep->dom->device);
 		ret = hipHostMalloc((void **)&mc->mask_host, 2 * LFA_CID_BYTES, 0) ==
@@ -285,15 +286,16 @@ static int join_impl(struct lfa_coll_ep *ep, lfa_addr_t coll_addr,
 			 * algorithm each member has selected for its collectives */
 			ret = run_device(ep, over, LFA_ALLREDUCE, dmask,
 					 (char *)dmask + LFA_CID_BYTES, LFA_CID_BYTES, -1,
-					 LFA_UINT8, LFA_BAND, ep->stream, LFA_ALGO_TREE);
+					 LFA_UINT8, LFA_BAND, ep->stream, LFA_ALGO_TREE, 0, NULL);
 			if (!ret)
 				hipMemcpyAsync(mc->mask_host, (char *)dmask + LFA_CID_BYTES,
 					       LFA_CID_BYTES, hipMemcpyDeviceToHost, ep->stream);
 		}
 		if (!ret)
-			ret = enqueue_completion(ep, ep->stream, context, 1, mc, 0, NULL);
-		if (!ret)
-			tag_p2p(ep, over, t0);
+			p = enqueue_completion(ep, ep->stream, context, PEND_JOIN, mc,
+					       (struct op_done){ 0, NULL }, &ret);
+		if (p)
+			tag_p2p(p, over, t0);
 	}
 	if (ret)
 		free_mask(ep, mc);
@@ -341,8 +343,8 @@ int lfa_mc_close(struct lfa_coll_mc *mc)
 	for (size_t i = 0; i < ep->qlen; i++) {
 		struct pending *p = &ep->q[(ep->qhead + i) % ep->qcap];
 
-		if (p->kind == 1 && p->mc == mc) {
-			p->kind = 2;
+		if (p->kind == PEND_JOIN && p->mc == mc) {
+			p->kind = PEND_JOIN_CLOSED;
 			p->mc = NULL;
 		}
 		if (p->pmc == mc) {

@@ -185,7 +185,7 @@ size_t lfa_coll_ep_stage_bytes(struct lfa_coll_ep *ep)
 
 /* A free pinned bounce block (2 x LFA_BOUNCE_BYTES), or NULL when all are
  * busy or none can be allocated (ep->lock held). */
-LFA_INTERNAL void *bounce_get(struct lfa_coll_ep *ep)
+static void *bounce_get(struct lfa_coll_ep *ep)
 {
 	for (int i = 0; i < LFA_BOUNCE_POOL; i++) {
 		struct bounce_buf *b = &ep->bounce[i];
@@ -235,14 +235,57 @@ LFA_INTERNAL void bounce_free_all(struct lfa_coll_ep *ep, int drained)
 	}
 }
 
-/* A completed hop's result to the caller's pageable buffer (the kernels
- * wrote it to the bounce block's mapping; the completion word or event
- * that ended the hop made it visible to the host). */
-static void bounce_finish(struct hop *h)
+/*
+ * Pageable host buffers of a small operation through a pinned bounce block:
+ * the input copied into the block on the CPU here, the kernels run on the
+ * block's mappings (*zin, *zout), the result copied back when the operation
+ * completes (bounce_finish) — no H2D / D2H copies and their events (2
+ * processes, 4 KiB: DESIGN.md §7 round 5).  A member with no result (a
+ * non-root member of a reduce, lfa_coll_io_bytes) gets *zout = NULL and
+ * nothing copied back: its kernels never write the block's output half,
+ * which still holds an earlier operation's bytes (an in-place
+ * caller's input was overwritten with them).  0, or -1 when the operation
+ * is too large or no block is free or mappable: *b is then empty and the
+ * block back in the pool.  ep->lock held.
+ */
+LFA_INTERNAL int bounce_acquire(struct lfa_coll_ep *ep, struct bounce *b,
+			  const struct lfa_coll_mc *mc, enum lfa_collective_op coll,
+			  const void *buf, void *result, size_t count, int root,
+			  size_t esz, void **zin, void **zout)
 {
-	if (h->bounce_bytes)
-		memcpy(h->bounce_user, h->bounce_out, h->bounce_bytes);
-	h->bounce_bytes = 0;
+	size_t in_b, out_b;
+	void *zi, *zo;
+
+	memset(b, 0, sizeof(*b));
+	lfa_coll_io_bytes(coll, count, mc->size, mc->rank, root, esz, &in_b, &out_b);
+	if (in_b > LFA_BOUNCE_BYTES || !(b->block = bounce_get(ep)))
+		return -1;
+	b->out = (char *)b->block + LFA_BOUNCE_BYTES;
+	zi = zero_copy_of(b->block, ep->dom->device);
+	zo = zero_copy_of(b->out, ep->dom->device);
+	if (!zi || !zo) {
+		bounce_put(ep, b->block);
+		memset(b, 0, sizeof(*b));
+		return -1;
+	}
+	if (coll == LFA_REDUCE && mc->rank != root)
+		result = NULL;
+	b->user = result;
+	b->bytes = result ? out_b : 0;
+	memcpy(b->block, buf, in_b);
+	*zin = zi;
+	*zout = result ? zo : NULL;
+	return 0;
+}
+
+/* A completed operation's result to the caller's pageable buffer (the
+ * kernels wrote it to the bounce block's mapping; the completion word or
+ * event that ended the operation made it visible to the host). */
+LFA_INTERNAL void bounce_finish(struct bounce *b)
+{
+	if (b->bytes)
+		memcpy(b->user, b->out, b->bytes);
+	b->bytes = 0;
 }
 
 LFA_INTERNAL void hop_free(struct hop *h)
@@ -277,7 +320,7 @@ LFA_INTERNAL void hop_free(struct hop *h)
 	}
 	/* after the stream sync above when the hop had not finished (a hop
 	 * that failed before it became a device hop never launched) */
-	bounce_put(h->ep, h->bounce);
+	bounce_put(h->ep, h->bounce.block);
 	free(h->r.reqs);
 	free(h);
 }
@@ -361,7 +404,7 @@ LFA_INTERNAL void host_progress_all(struct lfa_coll_ep *ep)
 
 				if (*(volatile uint64_t *)ep->done_word >= h->r.x.done_val) {
 					ep->word_ops++;
-					bounce_finish(h);
+					bounce_finish(&h->bounce);
 					h->done = 1;
 					LFA_TRACE("hop cid %#x done", (unsigned)h->r.cid);
 				} else if (i == 0 &&    /* only the head's bound runs */
@@ -379,7 +422,7 @@ LFA_INTERNAL void host_progress_all(struct lfa_coll_ep *ep)
 			last = h->out_ev ? h->out_ev : h->fin;
 			e = hipEventQuery(last);
 			if (e == hipSuccess) {
-				bounce_finish(h);
+				bounce_finish(&h->bounce);
 				h->done = 1;
 				LFA_TRACE("hop cid %#x done", (unsigned)h->r.cid);
 			} else if (e != hipErrorNotReady &&
@@ -389,24 +432,6 @@ LFA_INTERNAL void host_progress_all(struct lfa_coll_ep *ep)
 			h->done = 1;
 		}
 	}
-}
-
-LFA_INTERNAL int enqueue_host(struct lfa_coll_ep *ep, struct hop *h, void *context,
-			int kind, struct lfa_coll_mc *mc)
-{
-	struct pending *p = queue_slot(ep);
-
-	if (!p)
-		return -LFA_ENOMEM;
-	memset(p, 0, sizeof(*p));
-	p->hop = h;
-	p->context = context;
-	p->kind = kind;
-	p->mc = mc;
-	ep->qlen++;
-	/* kick: run up to the first transfer now (coll_progress_work) */
-	host_progress_all(ep);
-	return 0;
 }
 
 /* A handshake collective of hop `h` on its reserved seq (host buffers). */
@@ -424,8 +449,8 @@ static int sub_start(struct lfa_coll_ep *ep, struct hop *h, enum lfa_collective_
 	 * point of each member's calls, so the endpoint's algorithm then (the
 	 * caller may have selected another for later operations) can differ
 	 * between members */
-	ret = host_start(ep, h->sub, mc, coll, buf, result, count, -1, dt, op, 0,
-			 LFA_ALGO_TREE);
+	ret = host_start(ep, h->sub, mc, coll, buf, result, count, -1, dt, op,
+			 PLACE_HOST, LFA_ALGO_TREE);
 	h->sub->r.cid = (uint64_t)mc->group_id << 16 | seq;
 	LFA_TRACE("hop cid %#x handshake %d on cid %#x (mc seq now %u)", (unsigned)h->r.cid,
 		  (int)coll, (unsigned)h->sub->r.cid, (unsigned)mc->seq);
@@ -623,7 +648,7 @@ LFA_INTERNAL int run_host_chunked(struct lfa_coll_ep *ep, struct lfa_coll_mc *mc
 		hipStreamWaitEvent(ep->stream, h2d[slot], 0);
 		ret = run_device(ep, mc, coll, din,
 				 coll == LFA_BROADCAST ? din : dout, c.dev_count,
-				 root, dt, op, ep->stream, ep->algo);
+				 root, dt, op, ep->stream, ep->algo, 0, NULL);
 		hipEventRecord(comp[slot], ep->stream);
 		hipStreamWaitEvent(ep->d2h_stream, comp[slot], 0);
 		if (out)
@@ -665,7 +690,7 @@ LFA_INTERNAL int run_device_chunked(struct lfa_coll_ep *ep, struct lfa_coll_mc *
 				 &c) == 1; idx++)
 		ret = run_device(ep, mc, coll, buf ? (const char *)buf + c.src_off : NULL,
 				 result ? (char *)result + c.dst_off : NULL, c.dev_count,
-				 root, dt, op, ep->stream, ep->algo);
+				 root, dt, op, ep->stream, ep->algo, 0, NULL);
 	return ret;
 }
 
@@ -674,20 +699,23 @@ LFA_INTERNAL int run_device_chunked(struct lfa_coll_ep *ep, struct lfa_coll_mc *
  * the caller mixes a device buf with a host result.) */
 LFA_INTERNAL int run_host_whole(struct lfa_coll_ep *ep, struct lfa_coll_mc *mc,
 			  enum lfa_collective_op coll, const void *buf,
-			  size_t in_bytes, void *result, size_t out_bytes,
-			  size_t count, int root, enum lfa_datatype dt,
-			  enum lfa_op op)
+			  void *result, size_t count, int root,
+			  enum lfa_datatype dt, enum lfa_op op)
 {
+	size_t in_bytes, out_bytes;
 	char *din, *dout;
 	int ret;
 
+	lfa_coll_io_bytes(coll, count, mc->size, mc->rank, root,
+			  lfa_reduce_datatype_size(dt), &in_bytes, &out_bytes);
 	if (grow_staging(ep, in_bytes + out_bytes + 32))
 		return -LFA_ENOMEM;
 	din = ep->hs[0];
 	dout = din + ((in_bytes + 15) & ~(size_t)15);
 	if (buf && in_bytes)
 		hipMemcpyAsync(din, buf, in_bytes, hipMemcpyDefault, ep->stream);
-	ret = run_device(ep, mc, coll, din, dout, count, root, dt, op, ep->stream, ep->algo);
+	ret = run_device(ep, mc, coll, din, dout, count, root, dt, op, ep->stream, ep->algo,
+			 0, NULL);
 	if (!ret && result && out_bytes)
 		hipMemcpyAsync(result, dout, out_bytes, hipMemcpyDefault,
 			       ep->stream);
@@ -700,18 +728,19 @@ LFA_INTERNAL int run_host_whole(struct lfa_coll_ep *ep, struct lfa_coll_mc *mc,
 LFA_INTERNAL int host_start(struct lfa_coll_ep *ep, struct hop *h,
 		      struct lfa_coll_mc *mc, enum lfa_collective_op coll,
 		      const void *buf, void *result, size_t count, int root,
-		      enum lfa_datatype dt, enum lfa_op op, int dev,
+		      enum lfa_datatype dt, enum lfa_op op, enum placement where,
 		      enum lfa_coll_algo algo)
 {
 	size_t esz = lfa_reduce_datatype_size(dt);
 	/* this operation's sequence number, taken before a P2P handshake below
 	 * draws the next ones */
 	const uint16_t seq = (uint16_t)(mc->seq - 1);
+	enum placement place = where;
 	struct plan raw;
-	int ret, sym;
+	int ret, sym, dev;
 
 	h->ep = ep;
-	if (dev == 2) {
+	if (where == PLACE_HOST_DEV) {
 		/* host buffers the GPU reaches (pinned, registered): the device
 		 * schedule runs on their mappings — this member's kernels alone
 		 * touch its buf and result (peers only see the symmetric
@@ -719,45 +748,19 @@ LFA_INTERNAL int host_start(struct lfa_coll_ep *ep, struct hop *h,
 		void *zb = buf ? zero_copy_of(buf, ep->dom->device) : NULL;
 		void *zr = result ? zero_copy_of(result, ep->dom->device) : NULL;
 
-		if ((!buf || zb) && (!result || zr)) {
+		if ((!buf || zb) && (!result || zr))
+			place = PLACE_MAPPED;
+		else if (!bounce_acquire(ep, &h->bounce, mc, coll, buf, result, count, root,
+					 esz, &zb, &zr))
+			place = PLACE_BOUNCED;
+		else
+			place = PLACE_STAGED;
+		if (place != PLACE_STAGED) {
 			buf = zb;
 			result = zr;
-			dev = 1;
-		} else if (count * esz <= LFA_BOUNCE_BYTES && (h->bounce = bounce_get(ep))) {
-			/* pageable buffers of a small operation: the input copied
-			 * into a pinned bounce block on the CPU, the schedule run on
-			 * the block's mapping, the result copied back when the hop
-			 * completes — no H2D / D2H copies and their events (2
-			 * processes, 4 KiB: DESIGN.md §7 round 5) */
-			char *bin = h->bounce, *bout = bin + LFA_BOUNCE_BYTES;
-			size_t moff, mlen;
-
-			lfa_coll_block(count, mc->size, mc->rank, &moff, &mlen);
-			/* a non-root member of a reduce has no result: the kernels never
-			 * write the block's output half, so nothing is copied back
-			 * (the half still held an earlier operation's bytes,
-			 * and an in-place caller's input was overwritten with them) —
-			 * the staged path's out_bytes rule below */
-			if (coll == LFA_REDUCE && mc->rank != root)
-				result = NULL;
-			h->bounce_out = bout;
-			h->bounce_user = result;
-			h->bounce_bytes = !result ? 0 : coll == LFA_REDUCE_SCATTER ? mlen * esz :
-					  count * esz;
-			zb = zero_copy_of(bin, ep->dom->device);
-			zr = zero_copy_of(bout, ep->dom->device);
-			if (!zb || !zr) {
-				bounce_put(ep, h->bounce);
-				h->bounce = NULL;
-				h->bounce_bytes = 0;
-			} else {
-				memcpy(bin, buf, count * esz);
-				buf = zb;
-				result = result ? zr : NULL;
-				dev = 1;
-			}
 		}
 	}
+	dev = place != PLACE_HOST;      /* the device schedule (xport_peer_dev) */
 	/* P2P keeps its schedule on device buffers (the peers' symmetric
 	 * workspaces are IPC-mapped device memory; its barriers become zero-byte
 	 * messages); host buffers and RCCL run as TREE */
@@ -790,9 +793,9 @@ LFA_INTERNAL int host_start(struct lfa_coll_ep *ep, struct hop *h,
 		h->sub_seq = mc->seq;
 		mc->seq += 2;
 	}
-	h->dev = dev != 0;
+	h->dev = dev;
 	h->r.stream = ep->stream;
-	if (dev == 1 && sym && h->pl.nsteps == 1 && h->pl.steps[0].type == LFA_STEP_ONESHOT &&
+	if (place != PLACE_STAGED && dev && sym && h->pl.nsteps == 1 && h->pl.steps[0].type == LFA_STEP_ONESHOT &&
 	    ep->done_word) {
 		/* one kernel in place on device buffers: it ends in the
 		 * completion word, no event */
@@ -807,13 +810,12 @@ LFA_INTERNAL int host_start(struct lfa_coll_ep *ep, struct hop *h,
 	} else if (h->pl.tmp && !(h->tmp = malloc(h->pl.tmp))) {
 		return -LFA_ENOMEM;
 	}
-	if (dev == 2) {
+	if (place == PLACE_STAGED) {
 		/* host buffers through device copies (reducing collectives) */
-		size_t moff, mlen, in_b = count * esz;
+		size_t in_b;
 
-		lfa_coll_block(count, mc->size, mc->rank, &moff, &mlen);
-		h->out_bytes = coll == LFA_REDUCE_SCATTER ? mlen * esz :
-			       coll == LFA_REDUCE && mc->rank != root ? 0 : count * esz;
+		lfa_coll_io_bytes(coll, count, mc->size, mc->rank, root, esz, &in_b,
+				  &h->out_bytes);
 		h->user_out = result;
 		if (!(h->st_in = stage_get(ep, in_b)) ||
 		    !(h->st_out = stage_get(ep, h->out_bytes)))
@@ -846,27 +848,30 @@ LFA_INTERNAL int host_submit(struct lfa_coll_ep *ep, struct lfa_coll_mc *mc,
 		       enum lfa_collective_op coll, const void *buf,
 		       void *result, size_t count, int root,
 		       enum lfa_datatype dt, enum lfa_op op, void *context,
-		       int kind, struct lfa_coll_mc *jmc, int dev,
-		       enum lfa_coll_algo algo)
+		       enum pending_kind kind, struct lfa_coll_mc *jmc,
+		       enum placement where, enum lfa_coll_algo algo, uint64_t chain)
 {
 	struct hop *h = calloc(1, sizeof(*h));
 	const uint64_t t0 = mc->p2p_ticket;
+	struct pending *p = NULL;
 	int ret;
 
 	if (!h)
 		return -LFA_ENOMEM;
 	mc->seq++;                              /* coll_get_next_id :48-52 */
-	ret = host_start(ep, h, mc, coll, buf, result, count, root, dt, op, dev, algo);
+	ret = host_start(ep, h, mc, coll, buf, result, count, root, dt, op, where, algo);
 	LFA_TRACE("submit cid %#x coll %d count %zu dev %d algo %d phase %d sub_seq %u -> %d",
-		  (unsigned)h->r.cid, (int)coll, count, dev, (int)algo, h->phase,
+		  (unsigned)h->r.cid, (int)coll, count, (int)where, (int)algo, h->phase,
 		  (unsigned)h->sub_seq, ret);
 	if (!ret)
-		ret = enqueue_host(ep, h, context, kind, jmc);
-	if (ret)
+		p = enqueue_host(ep, h, context, kind, jmc, &ret);
+	if (!p) {
 		hop_free(h);
-	else
-		tag_p2p(ep, mc, t0);
-	return ret;
+		return ret;
+	}
+	p->chain = chain;
+	tag_p2p(p, mc, t0);
+	return 0;
 }
 
 /*
@@ -894,7 +899,7 @@ LFA_INTERNAL int peer_submit_chunked(struct lfa_coll_ep *ep, struct lfa_coll_mc 
 			       enum lfa_collective_op coll, const void *buf,
 			       void *result, size_t count, int root,
 			       enum lfa_datatype dt, enum lfa_op op, void *context,
-			       int dev, size_t chunk)
+			       enum placement where, size_t chunk)
 {
 	const size_t esz = lfa_reduce_datatype_size(dt);
 	const uint64_t chain = ++ep->next_chain;
@@ -915,7 +920,8 @@ LFA_INTERNAL int peer_submit_chunked(struct lfa_coll_ep *ep, struct lfa_coll_mc 
 		void *r = result ? (char *)result + off * esz : NULL;
 
 		ret = host_submit(ep, mc, coll, (const char *)buf + off * esz, r, n, root,
-				  dt, op, context, last ? 0 : 3, NULL, dev, ep->algo);
+				  dt, op, context, last ? PEND_COLL : PEND_CHUNK, NULL, where,
+				  ep->algo, chain);
 
 		if (ret) {
 			/* the caller is told the operation never started: the
@@ -928,7 +934,6 @@ LFA_INTERNAL int peer_submit_chunked(struct lfa_coll_ep *ep, struct lfa_coll_mc 
 				ep->failed_chain = chain;
 			return ret;
 		}
-		ep->q[(ep->qhead + ep->qlen - 1) % ep->qcap].chain = chain;
 	}
 	return 0;
 }

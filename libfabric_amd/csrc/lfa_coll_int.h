@@ -1,8 +1,9 @@
 /*
  * lfa_coll_int.h — internal types shared by the collective provider's
  * translation units (liblfa_coll.so): the domain / endpoint / group state
- * (lfa_coll.c), the executor and its transports (lfa_coll_exec.c) and the
- * single-GPU loopback (lfa_coll_loopback.c).  Not installed.
+ * (lfa_coll.c), the queue of in-flight operations (lfa_coll_cq.c), the
+ * executor and its transports (lfa_coll_exec.c) and the single-GPU loopback
+ * (lfa_coll_loopback.c).  Not installed.
  */
 #ifndef LFA_COLL_INT_H
 #define LFA_COLL_INT_H
@@ -24,7 +25,8 @@
 
 #define LFA_MAX_GROUP_ID 256            /* OFI_MAX_GROUP_ID, ofi_coll.h:44 */
 #define LFA_CID_BYTES (LFA_MAX_GROUP_ID / 8)
-/* Bytes of one P2P handle-exchange record (struct sym_rec, lfa_coll.c). */
+/* Bytes of one P2P handle-exchange record (struct sym_rec below, the
+ * handshake of lfa_coll_ws.c). */
 #define LFA_SYM_REC_BYTES 80
 #define LFA_STAGE_POOL 128              /* peer-domain staging buffers kept */
 #define LFA_BOUNCE_POOL 8               /* pinned host bounce blocks kept */
@@ -106,23 +108,55 @@ struct lfa_coll_domain {
 
 struct hop;
 
+/* How a launch completes: its kernel stores `val` into the completion word
+ * `w` (NULL: the endpoint's done_word), no event.  All zero: through an
+ * event. */
+struct op_done {
+	uint64_t val;
+	const uint64_t *w;
+};
+
+/* What reaping a queued operation posts. */
+enum pending_kind {
+	PEND_COLL,              /* a collective: a CQ entry */
+	PEND_JOIN,              /* a join: join_finish, an EQ entry */
+	PEND_JOIN_CLOSED,       /* a join whose handle was closed: nothing */
+	PEND_CHUNK,             /* a non-final chunk of a collective: nothing */
+};
+
+/* Where a peer domain's operation runs.  Callers of host_start pass one of
+ * the first three; host_start resolves PLACE_HOST_DEV to one of the rest. */
+enum placement {
+	PLACE_HOST,             /* host buffers, the host schedule */
+	PLACE_DEVICE,           /* device buffers in place */
+	PLACE_HOST_DEV,         /* host buffers on the device schedule: */
+	PLACE_MAPPED,           /*   pinned: on their zero-copy mappings */
+	PLACE_BOUNCED,          /*   pageable, small: through a bounce block */
+	PLACE_STAGED,           /*   else copied through device staging */
+};
+
+/* A pageable operation run through a pinned bounce block (ep->bounce): the
+ * input is copied into the block's first half at submit (bounce_acquire), the
+ * kernels run on the block's mappings, and `bytes` of its second half `out`
+ * go to `user` when the operation completes (bounce_finish). */
+struct bounce {
+	void *block, *out, *user;
+	size_t bytes;
+};
+
 struct pending {
 	hipEvent_t ev;          /* device domains */
 	struct hop *hop;        /* host domains: the operation's state */
 	void *context;
-	int kind;               /* 0 collective, 1 join, 2 join of a closed mc,
-				 * 3 a non-final chunk of a collective (no entry) */
+	enum pending_kind kind;
 	struct lfa_coll_mc *mc;
 	/* the group the operation's P2P kernels ran on and its highest ticket
 	 * (0: none); timed_out: found failed when that group was closed */
 	struct lfa_coll_mc *pmc;
 	uint64_t ticket;
 	int timed_out;
-	/* device domains: completes when the endpoint's completion word reaches
-	 * done_val (the one-shot kernel wrote it; no event), 0: the event;
-	 * done_w: that word (NULL: the endpoint's done_word) */
-	uint64_t done_val;
-	const uint64_t *done_w;
+	/* device domains: completes through a completion word, or the event */
+	struct op_done done;
 	/* word operations: when the operation fails if its word has not come,
 	 * and when the queue or stream owing it was last asked for an error
 	 * (lfa_coll.c word_overdue); armed: the bound runs from the first poll
@@ -133,10 +167,8 @@ struct pending {
 		int armed;
 	} ww;
 	/* device domains: a one-member group's operation on pageable host
-	 * buffers run through a pinned bounce block (ep->bounce); its result is
-	 * copied to bounce_user when the operation is reaped */
-	void *bounce, *bounce_out, *bounce_user;
-	size_t bounce_bytes;
+	 * buffers; its result is copied out when the operation is reaped */
+	struct bounce bounce;
 	/* the chunks of one chunked operation (peer_submit_chunked) share a
 	 * nonzero chain id: the operation posts ONE completion — the first
 	 * chunk's error, or the last chunk's success */
@@ -198,17 +230,14 @@ struct lfa_coll_ep {
 	uint32_t *done_ctr;         /* device, 0 at rest */
 	uint64_t *done_word;        /* host-mapped */
 	uint64_t done_seq;
-	uint64_t op_done_val;       /* run_device's last launch's value, or 0 */
-	const uint64_t *op_done_w;  /* ... and its word (NULL: done_word) */
 	/* direct dispatch (lfa_signal.h lfa_direct_*): a one-member group's
 	 * small reducing collective as liblfa's own AQL packet on its own HSA
 	 * queue (one per device and process, shared by its endpoints), with its
-	 * own counter and word (kernels there are not ordered with ep->stream).
-	 * Taken at first use; LFA_DIRECT=0 keeps the HIP
-	 * launch.  allow_direct: set by submit around a caller's operation (the
-	 * barrier's own staging copy is stream-ordered, so it never goes direct) */
+	 * own counter and word (kernels there are not ordered with ep->stream,
+	 * so only run_solo's callers that need no stream order ask for it).
+	 * Taken at first use; LFA_DIRECT=0 keeps the HIP launch. */
 	struct lfa_direct *direct;
-	int direct_tried, allow_direct;
+	int direct_tried;
 	uint32_t *ddone_ctr;
 	uint64_t *ddone_word;
 	uint64_t ddone_seq;
@@ -288,11 +317,6 @@ struct xrun {
 	int hip_err;            /* first failing HIP call's code (prov_errno) */
 };
 
-/*
- * A HIP call of an operation failed: keep the first code (it becomes the
- * completion's prov_errno, fi_cq_err_entry's provider-specific error) and,
- * with LFA_DEBUG set, name the call on stderr.  Returns the call's result.
- */
 /* LFA_TRACE=1: one stderr line per hop state change (diagnostics). */
 static int lfa_trace_on __attribute__((unused)) = -1;
 #define LFA_TRACE(...)                                                        \
@@ -309,34 +333,6 @@ static int lfa_trace_on __attribute__((unused)) = -1;
 			fputc('\n', stderr);                                  \
 		}                                                             \
 	} while (0)
-
-LFA_INTERNAL hipError_t lfa_hip_note(int *slot, hipError_t e, const char *what);
-
-/* lfa_coll_exec.c */
-LFA_INTERNAL void *resolve(const struct xctx *x, struct lfa_ref r);
-/* Non-communication step on `stream`. */
-LFA_INTERNAL int run_local(const struct lfa_step *s, const struct lfa_ref *refs,
-			   const struct xctx *x, enum lfa_op op, enum lfa_datatype dt,
-			   hipStream_t stream);
-LFA_INTERNAL int plan_uses_sym(const struct lfa_step *st, size_t nsteps);
-LFA_INTERNAL size_t sym_region(size_t count, size_t esz);
-/* Bytes per workspace region the plan needs (ONESHOT: 2·n slots). */
-LFA_INTERNAL size_t plan_sym_need(const struct lfa_step *st, size_t nsteps, int n,
-				  size_t count, size_t esz);
-LFA_INTERNAL int xrun_advance(struct xrun *r);
-/* BARRIER of a plan on the symmetric workspace: the flag-barrier kernel. */
-LFA_INTERNAL int sig_barrier(struct xrun *r);
-/* ONESHOT step: the one-kernel small allreduce (lfa_signal.h). */
-LFA_INTERNAL int sig_oneshot(struct xrun *r, const struct lfa_step *st);
-/* x->done_val receives the one-shot launch's completion-word value (0: the
- * operation completes through an event). */
-LFA_INTERNAL int exec_plan(struct lfa_coll_mc *mc, const struct plan *pl,
-			   struct xctx *x, enum lfa_op op, enum lfa_datatype dt,
-			   hipStream_t s);
-LFA_INTERNAL extern const struct xport xport_peer, xport_peer_dev;
-
-/* lfa_coll.c */
-LFA_INTERNAL int check_reduce_args(enum lfa_datatype dt, enum lfa_op op);
 
 /* One member's record in the P2P workspace handshake (lfa_coll_ws.c): its
  * export succeeded, the IPC handle, the workspace's identity word. */
@@ -367,11 +363,9 @@ struct hop {
 	size_t out_bytes;
 	hipEvent_t in_ev, out_ev;
 	int in_waited;
-	/* pageable host buffers of a small operation: a pinned bounce block
-	 * (ep->bounce) holds the input and the result; the result is copied to
-	 * bounce_user on the CPU when the hop completes (bounce_finish) */
-	void *bounce, *bounce_out, *bounce_user;
-	size_t bounce_bytes;
+	/* pageable host buffers of a small operation (PLACE_BOUNCED); the
+	 * result is copied out on the CPU when the hop completes */
+	struct bounce bounce;
 	/* a device hop whose every item is on the stream: a later P2P hop may
 	 * enqueue behind it (stream order) without waiting for it to finish */
 	int issued;
@@ -396,20 +390,35 @@ enum { HOP_RUN, HOP_WAIT_PRIOR, HOP_SYM_GATHER, HOP_SYM_AGREE };
 #define LFA_DEFAULT_CHUNK (32u << 20)
 
 /* Internal entry points shared by the provider's translation units. */
+
 /* lfa_coll.c */
 LFA_INTERNAL struct lfa_coll_mc *mc_of(struct lfa_coll_ep *ep, lfa_addr_t a);
-LFA_INTERNAL void release_event(struct lfa_coll_ep *ep, hipEvent_t ev);
-LFA_INTERNAL hipEvent_t event_get(struct lfa_coll_ep *ep);
-LFA_INTERNAL int queue_reserve(struct lfa_coll_ep *ep, size_t n);
-LFA_INTERNAL struct pending *queue_slot(struct lfa_coll_ep *ep);
-LFA_INTERNAL int enqueue_completion(struct lfa_coll_ep *ep, hipStream_t s,
-			      void *context, int kind, struct lfa_coll_mc *mc,
-			      uint64_t done_val, const uint64_t *done_w);
+LFA_INTERNAL int mc_member(const struct lfa_coll_mc *mc);
+LFA_INTERNAL int check_reduce_args(enum lfa_datatype dt, enum lfa_op op);
+/* One operation on device buffers, enqueued on `s`.  direct: a solo copy may
+ * go through the direct queue (nothing on the stream must precede it).
+ * *done (may be NULL: the caller records an event) receives how the launch
+ * completes. */
 LFA_INTERNAL int run_device(struct lfa_coll_ep *ep, struct lfa_coll_mc *mc,
 		      enum lfa_collective_op coll, const void *buf, void *result,
 		      size_t count, int root, enum lfa_datatype dt,
-		      enum lfa_op op, hipStream_t s, enum lfa_coll_algo algo);
-LFA_INTERNAL int mc_member(const struct lfa_coll_mc *mc);
+		      enum lfa_op op, hipStream_t s, enum lfa_coll_algo algo,
+		      int direct, struct op_done *done);
+
+/* lfa_coll_cq.c */
+LFA_INTERNAL void release_event(struct lfa_coll_ep *ep, hipEvent_t ev);
+LFA_INTERNAL hipEvent_t event_get(struct lfa_coll_ep *ep);
+LFA_INTERNAL int queue_reserve(struct lfa_coll_ep *ep, size_t n);
+/* Both return the queued operation's slot (valid until it is reaped), or
+ * NULL with the error in *err. */
+LFA_INTERNAL struct pending *enqueue_completion(struct lfa_coll_ep *ep, hipStream_t s,
+					  void *context, enum pending_kind kind,
+					  struct lfa_coll_mc *mc, struct op_done done,
+					  int *err);
+LFA_INTERNAL struct pending *enqueue_host(struct lfa_coll_ep *ep, struct hop *h,
+				    void *context, enum pending_kind kind,
+				    struct lfa_coll_mc *mc, int *err);
+
 /* lfa_coll_word.c */
 LFA_INTERNAL int word_overdue(const struct lfa_coll_ep *ep, const uint64_t *w, hipStream_t s,
 			struct word_wait *ww, int *perr);
@@ -417,11 +426,12 @@ LFA_INTERNAL int done_word_init(struct lfa_coll_ep *ep);
 LFA_INTERNAL void done_word_free(struct lfa_coll_ep *ep, int stream_ok);
 LFA_INTERNAL size_t solo_bytes(void);
 LFA_INTERNAL int run_solo(struct lfa_coll_ep *ep, const void *buf, void *result, size_t count,
-		    enum lfa_datatype dt);
+		    enum lfa_datatype dt, int direct, struct op_done *done);
+
 /* lfa_coll_ws.c */
 LFA_INTERNAL void sig_word_free(struct lfa_coll_mc *mc);
 LFA_INTERNAL int sig_ready(struct lfa_coll_mc *mc);
-LFA_INTERNAL void tag_p2p(struct lfa_coll_ep *ep, struct lfa_coll_mc *mc, uint64_t t0);
+LFA_INTERNAL void tag_p2p(struct pending *p, struct lfa_coll_mc *mc, uint64_t t0);
 LFA_INTERNAL int p2p_timed_out(const struct pending *p);
 LFA_INTERNAL void ws_domain_ref(int delta);
 LFA_INTERNAL void p2p_release(struct lfa_coll_mc *mc);
@@ -431,19 +441,22 @@ LFA_INTERNAL void sym_prepare(struct lfa_coll_mc *mc, size_t region, int ok,
 LFA_INTERNAL int sym_open(struct lfa_coll_mc *mc, const struct sym_rec *recs, size_t region,
 		    int *why);
 LFA_INTERNAL int p2p_ensure(struct lfa_coll_mc *mc, size_t region);
+
 /* lfa_coll_host.c */
 LFA_INTERNAL int is_device_ptr(const void *p);
 LFA_INTERNAL void *zero_copy_of(const void *p, int dev);
 LFA_INTERNAL int grow_staging(struct lfa_coll_ep *ep, size_t need);
 LFA_INTERNAL void stage_trim(struct lfa_coll_ep *ep, size_t keep);
-LFA_INTERNAL void *bounce_get(struct lfa_coll_ep *ep);
+LFA_INTERNAL int bounce_acquire(struct lfa_coll_ep *ep, struct bounce *b,
+			  const struct lfa_coll_mc *mc, enum lfa_collective_op coll,
+			  const void *buf, void *result, size_t count, int root,
+			  size_t esz, void **zin, void **zout);
+LFA_INTERNAL void bounce_finish(struct bounce *b);
 LFA_INTERNAL void bounce_put(struct lfa_coll_ep *ep, void *p);
 LFA_INTERNAL void bounce_retire(struct lfa_coll_ep *ep, void *p);
 LFA_INTERNAL void bounce_free_all(struct lfa_coll_ep *ep, int drained);
 LFA_INTERNAL void hop_free(struct hop *h);
 LFA_INTERNAL void host_progress_all(struct lfa_coll_ep *ep);
-LFA_INTERNAL int enqueue_host(struct lfa_coll_ep *ep, struct hop *h, void *context,
-			int kind, struct lfa_coll_mc *mc);
 LFA_INTERNAL int run_host_chunked(struct lfa_coll_ep *ep, struct lfa_coll_mc *mc,
 			    enum lfa_collective_op coll, const void *buf,
 			    void *result, size_t count, int root,
@@ -454,28 +467,56 @@ LFA_INTERNAL int run_device_chunked(struct lfa_coll_ep *ep, struct lfa_coll_mc *
 			      enum lfa_datatype dt, enum lfa_op op, size_t chunk);
 LFA_INTERNAL int run_host_whole(struct lfa_coll_ep *ep, struct lfa_coll_mc *mc,
 			  enum lfa_collective_op coll, const void *buf,
-			  size_t in_bytes, void *result, size_t out_bytes,
-			  size_t count, int root, enum lfa_datatype dt,
-			  enum lfa_op op);
+			  void *result, size_t count, int root,
+			  enum lfa_datatype dt, enum lfa_op op);
 LFA_INTERNAL int host_start(struct lfa_coll_ep *ep, struct hop *h,
 		      struct lfa_coll_mc *mc, enum lfa_collective_op coll,
 		      const void *buf, void *result, size_t count, int root,
-		      enum lfa_datatype dt, enum lfa_op op, int dev,
+		      enum lfa_datatype dt, enum lfa_op op, enum placement where,
 		      enum lfa_coll_algo algo);
+/* chain: the chunked operation this one is a chunk of (0: none) */
 LFA_INTERNAL int host_submit(struct lfa_coll_ep *ep, struct lfa_coll_mc *mc,
 		       enum lfa_collective_op coll, const void *buf,
 		       void *result, size_t count, int root,
 		       enum lfa_datatype dt, enum lfa_op op, void *context,
-		       int kind, struct lfa_coll_mc *jmc, int dev,
-		       enum lfa_coll_algo algo);
+		       enum pending_kind kind, struct lfa_coll_mc *jmc,
+		       enum placement where, enum lfa_coll_algo algo, uint64_t chain);
 LFA_INTERNAL size_t peer_chunked(const struct lfa_coll_ep *ep, const struct lfa_coll_mc *mc,
 			   enum lfa_collective_op coll, size_t count, size_t esz);
 LFA_INTERNAL int peer_submit_chunked(struct lfa_coll_ep *ep, struct lfa_coll_mc *mc,
 			       enum lfa_collective_op coll, const void *buf,
 			       void *result, size_t count, int root,
 			       enum lfa_datatype dt, enum lfa_op op, void *context,
-			       int dev, size_t chunk);
+			       enum placement where, size_t chunk);
+
 /* lfa_coll_group.c */
 LFA_INTERNAL void join_finish(struct lfa_coll_ep *ep, struct lfa_coll_mc *mc);
+
+/* lfa_coll_exec.c */
+/* A HIP call of an operation failed: keep the first code (it becomes the
+ * completion's prov_errno, fi_cq_err_entry's provider-specific error) and,
+ * with LFA_DEBUG set, name the call on stderr.  Returns the call's result. */
+LFA_INTERNAL hipError_t lfa_hip_note(int *slot, hipError_t e, const char *what);
+LFA_INTERNAL void *resolve(const struct xctx *x, struct lfa_ref r);
+/* Non-communication step on `stream`. */
+LFA_INTERNAL int run_local(const struct lfa_step *s, const struct lfa_ref *refs,
+			   const struct xctx *x, enum lfa_op op, enum lfa_datatype dt,
+			   hipStream_t stream);
+LFA_INTERNAL int plan_uses_sym(const struct lfa_step *st, size_t nsteps);
+LFA_INTERNAL size_t sym_region(size_t count, size_t esz);
+/* Bytes per workspace region the plan needs (ONESHOT: 2·n slots). */
+LFA_INTERNAL size_t plan_sym_need(const struct lfa_step *st, size_t nsteps, int n,
+				  size_t count, size_t esz);
+LFA_INTERNAL int xrun_advance(struct xrun *r);
+/* BARRIER of a plan on the symmetric workspace: the flag-barrier kernel. */
+LFA_INTERNAL int sig_barrier(struct xrun *r);
+/* ONESHOT step: the one-kernel small allreduce (lfa_signal.h). */
+LFA_INTERNAL int sig_oneshot(struct xrun *r, const struct lfa_step *st);
+/* x->done_val receives the one-shot launch's completion-word value (0: the
+ * operation completes through an event). */
+LFA_INTERNAL int exec_plan(struct lfa_coll_mc *mc, const struct plan *pl,
+			   struct xctx *x, enum lfa_op op, enum lfa_datatype dt,
+			   hipStream_t s);
+LFA_INTERNAL extern const struct xport xport_peer, xport_peer_dev;
 
 #endif

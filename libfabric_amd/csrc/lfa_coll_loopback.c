@@ -36,8 +36,7 @@ int lfa_coll_loopback(enum lfa_collective_op coll, enum lfa_coll_algo algo,
 
 	if (n < 1 || n > 64 || !send || !result || !esz)
 		return -LFA_EINVAL;
-	if ((coll == LFA_ALLREDUCE || coll == LFA_REDUCE ||
-	     coll == LFA_REDUCE_SCATTER) && (ret = check_reduce_args(dt, op)))
+	if (coll_reduces(coll) && (ret = check_reduce_args(dt, op)))
 		return ret;
 	if (algo == LFA_ALGO_RCCL)
 		algo = LFA_ALGO_TREE;

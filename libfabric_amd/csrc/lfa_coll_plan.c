@@ -29,6 +29,33 @@ void lfa_coll_block(size_t count, int nranks, int r, size_t *off, size_t *len)
 	*off = rr * base + (rr < extra ? rr : extra);
 }
 
+void lfa_coll_io_bytes(enum lfa_collective_op coll, size_t count, int nranks,
+		       int rank, int root, size_t esz, size_t *in_bytes,
+		       size_t *out_bytes)
+{
+	size_t off, len;
+
+	*in_bytes = *out_bytes = count * esz;
+	switch (coll) {
+	case LFA_REDUCE_SCATTER:
+		lfa_coll_block(count, nranks, rank, &off, &len);
+		*out_bytes = len * esz;
+		break;
+	case LFA_REDUCE:
+		if (rank != root)
+			*out_bytes = 0;
+		break;
+	case LFA_ALLGATHER:
+		*out_bytes = (size_t)nranks * count * esz;
+		break;
+	case LFA_SCATTER:
+		*in_bytes = rank == root ? (size_t)nranks * count * esz : 0;
+		break;
+	default:
+		break;
+	}
+}
+
 struct planner {
 	struct lfa_step *steps;
 	size_t cap, n;
@@ -619,8 +646,7 @@ int lfa_coll_plan(enum lfa_collective_op coll, enum lfa_coll_algo algo,
 							       bytes <= lfa_os_ag_bytes());
 
 		if ((n > 1 || os1) && n <= LFA_TREE_MAX && n <= LFA_PUT_MAX &&
-		    (coll == LFA_ALLREDUCE || coll == LFA_REDUCE_SCATTER ||
-		     coll == LFA_REDUCE)) {
+		    coll_reduces(coll)) {
 			int ret = plan_p2p(&p, coll, r, n, root, count, esz);
 
 			if (ret)

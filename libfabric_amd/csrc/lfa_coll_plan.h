@@ -47,6 +47,12 @@ LFA_INTERNAL size_t lfa_os_rs_bytes(void);
 #define LFA_OS_AG_BYTES_DEFAULT (2u << 20)
 LFA_INTERNAL size_t lfa_os_ag_bytes(void);
 
+/* The collectives that combine their inputs with an lfa_op. */
+static inline int coll_reduces(enum lfa_collective_op coll)
+{
+	return coll == LFA_ALLREDUCE || coll == LFA_REDUCE || coll == LFA_REDUCE_SCATTER;
+}
+
 /* A heap-allocated plan. */
 struct plan {
 	struct lfa_step *steps;

@@ -287,19 +287,17 @@ LFA_INTERNAL size_t solo_bytes(void)
 }
 
 LFA_INTERNAL int run_solo(struct lfa_coll_ep *ep, const void *buf, void *result, size_t count,
-		    enum lfa_datatype dt)
+		    enum lfa_datatype dt, int direct, struct op_done *done)
 {
 	int ret;
 
-	ep->op_done_w = NULL;
-	if (ep->allow_direct && count * lfa_reduce_datatype_size(dt) <= LFA_DIRECT_SOLO_BYTES &&
+	if (direct && count * lfa_reduce_datatype_size(dt) <= LFA_DIRECT_SOLO_BYTES &&
 	    direct_of(ep) && !lfa_direct_failed(ep->direct)) {
 		/* no HIP launch: ~3 us less host time */
 		ret = lfa_direct_solo_copy(ep->direct, result, buf, count * lfa_reduce_datatype_size(dt),
 					   ep->ddone_ctr, ep->ddone_word, ep->ddone_seq + 1);
 		if (!ret) {
-			ep->op_done_val = ++ep->ddone_seq;
-			ep->op_done_w = ep->ddone_word;
+			*done = (struct op_done){ ++ep->ddone_seq, ep->ddone_word };
 			return 0;
 		}
 		if (ret != -LFA_EIO)
@@ -315,6 +313,6 @@ LFA_INTERNAL int run_solo(struct lfa_coll_ep *ep, const void *buf, void *result,
 				  ep->done_word, ep->done_seq + 1, ep->stream);
 	if (ret)
 		return ret;
-	ep->op_done_val = ++ep->done_seq;
+	*done = (struct op_done){ ++ep->done_seq, NULL };
 	return 0;
 }

@@ -54,13 +54,10 @@ LFA_INTERNAL int sig_ready(struct lfa_coll_mc *mc)
 }
 
 /* The operation just queued ran P2P kernels on `mc` if its ticket moved. */
-LFA_INTERNAL void tag_p2p(struct lfa_coll_ep *ep, struct lfa_coll_mc *mc, uint64_t t0)
+LFA_INTERNAL void tag_p2p(struct pending *p, struct lfa_coll_mc *mc, uint64_t t0)
 {
-	struct pending *p;
-
-	if (!ep->qlen || mc->p2p_ticket == t0)
+	if (mc->p2p_ticket == t0)
 		return;
-	p = &ep->q[(ep->qhead + ep->qlen - 1) % ep->qcap];
 	p->pmc = mc;
 	p->ticket = mc->p2p_ticket;
 }

@@ -209,6 +209,31 @@ def test_block_split():
             assert [(a, b - a) for a, b in oracle.slice_bounds(count, n)] == offs
 
 
+@pytest.mark.parametrize("n", [1, 2, 3, 8])
+def test_io_bytes(n):
+    """lfa_coll_io_bytes — what a member reads from buf and writes to result:
+    count·esz each, except reduce_scatter writes the member's block
+    (lfa_coll_block), reduce writes nothing off the root, allgather writes
+    n·count·esz, and scatter reads n·count·esz at the root, nothing elsewhere."""
+    BARRIER = 0
+    for kind in (BARRIER, BROADCAST, ALLREDUCE, ALLGATHER, REDUCE_SCATTER, REDUCE, SCATTER):
+        for count in (0, 1, n - 1, n, n + 1, 4099):
+            for esz in (1, 8):
+                for r in range(n):
+                    for root in range(n):
+                        want_in = want_out = count * esz
+                        if kind == REDUCE_SCATTER:
+                            want_out = coll.block(count, n, r)[1] * esz
+                        elif kind == REDUCE and r != root:
+                            want_out = 0
+                        elif kind == ALLGATHER:
+                            want_out = n * count * esz
+                        elif kind == SCATTER:
+                            want_in = n * count * esz if r == root else 0
+                        assert coll.io_bytes(kind, count, n, r, root, esz) == \
+                            (want_in, want_out), (kind, count, esz, r, root)
+
+
 @pytest.mark.parametrize("n", [2, 3])
 def test_tree_blocks_skewed_in_tmp(n):
     """Blocks of >= 1 MiB sit round_up(B, 256) + 6 KiB apart in TMP (HBM
