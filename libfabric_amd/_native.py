@@ -81,6 +81,11 @@ def _bind_lfa(L):
     L.lfa_host_reduce_tree.restype = c_int
     L.lfa_host_reduce_tree.argtypes = [c_int, c_int, c_void_p, ctypes.POINTER(c_void_p),
                                        c_int, c_size_t]
+    L.lfa_host_readwrite.restype = c_int
+    L.lfa_host_readwrite.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t]
+    L.lfa_host_swap.restype = c_int
+    L.lfa_host_swap.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_size_t]
 
 
 def _bind_tune(L):

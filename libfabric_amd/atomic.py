@@ -12,6 +12,8 @@ Mirrors the reference's L4 combine interface (include/ofi_atomic.h:45-90):
   writev / reduce_treev / host_writev  the fi_ioc (list) forms of write /
                                     reduce_tree / host_write: every segment of
                                     a list in one launch (fi_atomicv's shape)
+  host_readwrite / host_swap        the fetch and compare tables on host
+                                    buffers (lfa_host_readwrite / lfa_host_swap)
   reduce_valid / reduce_datatype_size  what write / reduce_tree / the
                                     collectives take: the table's columns plus
                                     DT.FLOAT16 and DT.BFLOAT16
@@ -266,6 +268,28 @@ def host_write(op: int, dt: int, dst, src, cnt: int | None = None) -> None:
     rc = lib().lfa_host_write(int(op), int(dt), _host_ptr(dst), _host_ptr(src), cnt)
     if rc:
         raise LfaError(rc, f"lfa_host_write({op},{dt})")
+
+
+def host_readwrite(op: int, dt: int, dst, src, res, cnt: int | None = None) -> None:
+    """res = dst; dst = dst OP src for HOST buffers (lfa_host_readwrite);
+    ATOMIC_READ takes src=None."""
+    if cnt is None:
+        cnt = dst.nbytes // datatype_size(dt)
+    rc = lib().lfa_host_readwrite(int(op), int(dt), _host_ptr(dst),
+                                  _host_ptr(src) if src is not None else None,
+                                  _host_ptr(res), cnt)
+    if rc:
+        raise LfaError(rc, f"lfa_host_readwrite({op},{dt})")
+
+
+def host_swap(op: int, dt: int, dst, src, cmp, res, cnt: int | None = None) -> None:
+    """res = dst; dst = src where (cmp OP dst) for HOST buffers (lfa_host_swap)."""
+    if cnt is None:
+        cnt = dst.nbytes // datatype_size(dt)
+    rc = lib().lfa_host_swap(int(op), int(dt), _host_ptr(dst), _host_ptr(src),
+                             _host_ptr(cmp), _host_ptr(res), cnt)
+    if rc:
+        raise LfaError(rc, f"lfa_host_swap({op},{dt})")
 
 
 def host_reduce_tree(op: int, dt: int, dst, srcs, cnt: int | None = None) -> None:

@@ -1,8 +1,10 @@
 """The oracle sweep's cases and inputs: no GPU, no product code.
 
 tests/test_sweep_gpu.py runs every (op, datatype) pair through every tree,
-tree-put and list-form kernel instantiation liblfa.so holds;
-tests/test_sweep_cpu.py runs the same cases through the host combine and
+tree-put and list-form kernel instantiation liblfa.so holds,
+tests/test_sweep_tables_gpu.py every entry of the write, fetch and compare
+tables through its own kernels (the last part of this module);
+tests/test_sweep_cpu.py runs the same cases through the host forms and
 checks the conditions below on the inputs themselves.  This module builds the
 cases: the pair lists, operands whose result depends on EVERY input, the byte
 offsets that send a launcher down each of its paths, and one arena per case
@@ -463,3 +465,301 @@ def treev_case(op, dt, nsrc, rng):
     want = [reference(op, dt, [data[k][i] for k in range(nsrc)]) if counts[i]
             else np.zeros(0, np.uint8) for i in range(nseg)]
     return ListCase(big, dst, src, want, f"treev op={op} dt={dt} nsrc={nsrc}")
+
+
+# --------------------------------------------------------- binary tables --
+# The three tables' own kernels: lfa_atomic_write_async (launch_write:
+# combine_lds / combine_elem / combine_unaligned), lfa_atomic_readwrite_async
+# and lfa_atomic_swap_async (launch_fetch: fetch_lds / fetch_elem with the
+# ALIGNED and the byte-wise functor).  Both launchers cut 16-KiB workgroup
+# tiles (4 waves x 4 KiB), so lanes() gives them two whole tiles, a partial
+# tile with whole and partial waves, and a ragged tail.
+
+CSWAP, CSWAP_NE, CSWAP_LE, CSWAP_LT, CSWAP_GE, CSWAP_GT, MSWAP = range(12, 19)
+N_RW_PAIRS = 145            # 119 entries of ops 0..9 + 13 ATOMIC_READ + 13 ATOMIC_WRITE
+N_SWAP_PAIRS = 84           # 2 x 13 (CSWAP, CSWAP_NE) + 4 x 12 ordered + 10 MSWAP
+WRITE_OPS = tuple(op for op in range(12) if op != READ)
+RW_OPS = tuple(range(12))
+SWAP_OPS = tuple(range(12, 19))
+
+# operands in the order the launcher classifies them (dst first)
+TABLE_OPERANDS = {"write": ("dst", "src"), "readwrite": ("dst", "res", "src"),
+                  "read": ("dst", "res"), "swap": ("dst", "src", "cmp", "res")}
+# who may be the one operand off the others' alignment, rotated by case index
+ODD = {"elem": ("src", "res", "cmp"), "bytes": ("src", "res", "cmp", "dst")}
+
+
+def rw_pairs():
+    return [(op, dt) for op in RW_OPS for dt in oracle.DT_NP if oracle.has_readwrite(op, dt)]
+
+
+def swap_pairs():
+    return [(op, dt) for op in SWAP_OPS for dt in oracle.DT_NP if oracle.has_swap(op, dt)]
+
+
+def table_dts(pairs, op):
+    return [dt for o, dt in pairs if o == op]
+
+
+def n_table_cases(dts, paths=PATHS) -> int:
+    return sum(len([p for p in paths_of(esz_of(dt)) if p in paths]) for dt in dts)
+
+
+def table_layout(esz: int, path: str, names, k: int = 0):
+    """(byte offsets past a 16-byte boundary per operand of `names`, the odd
+    operand or None) for launch_write / launch_fetch to take `path`.
+
+    vec    every operand 16-byte aligned
+    head   every operand esz bytes past a boundary: element head, vector
+           body, and the element tail the size then leaves (the vec path's
+           tail is there at every element size below 16)
+    elem   one operand (src, res or cmp: the k-th of those the call has) one
+           element further on than the rest: fetch_elem / combine_elem alone
+    bytes  one operand (those and dst) one byte off: the byte-wise functor
+    """
+    assert path in paths_of(esz), (esz, path)
+    offs = dict.fromkeys(names, esz if path == "head" else 0)
+    odd = None
+    if path in ODD:
+        cands = [o for o in ODD[path] if o in names]
+        odd = cands[k % len(cands)]
+        offs[odd] = esz if path == "elem" else 1
+    order = [offs[o] for o in names]
+    assert expect_path(esz, order[:1], order[1:]) == path, (esz, path, names, odd)
+    return order, odd
+
+
+def reference_readwrite(op: int, dt: int, dst, src) -> np.ndarray:
+    """The new dst of oracle.readwrite (byte arrays; src None: ATOMIC_READ)."""
+    nd = oracle.DT_NP[dt]
+    d = np.ascontiguousarray(dst).view(nd).copy()
+    s = np.ascontiguousarray(dst if src is None else src).view(nd).copy()
+    r = np.zeros_like(d)
+    oracle.readwrite(op, dt, d, s, r)
+    assert np.array_equal(r.view(np.uint8), np.ascontiguousarray(dst)), "oracle: res != old dst"
+    return d.view(np.uint8)
+
+
+def reference_swap(op: int, dt: int, dst, src, cmp) -> np.ndarray:
+    """The new dst of oracle.swap's shipping (CAS) variant (byte arrays)."""
+    nd = oracle.DT_NP[dt]
+    d = np.ascontiguousarray(dst).view(nd).copy()
+    r = np.zeros_like(d)
+    oracle.swap(op, dt, d, np.ascontiguousarray(src).view(nd).copy(),
+                np.ascontiguousarray(cmp).view(nd).copy(), r, oracle.CAS)
+    assert np.array_equal(r.view(np.uint8), np.ascontiguousarray(dst)), "oracle: res != old dst"
+    return d.view(np.uint8)
+
+
+# ----------------------------------------------------------- swap inputs --
+
+def is_complex(dt: int) -> bool:
+    return dt not in HALF and oracle.DT_NP[dt].kind == "c"
+
+
+def _signed(dt: int) -> bool:
+    return oracle.DT_NP[dt].kind == "i" or dt == oracle.DT_CODE["INT128"]
+
+
+def _draw(dt: int, n: int, rng) -> np.ndarray:
+    """n values of dt as (n, esz) bytes: integers uniform over the type,
+    floats (each component of a complex) uniform in (-2, 2)."""
+    if is_float(dt):
+        return _floats(dt, rng.uniform(-2.0, 2.0, n * (2 if is_complex(dt) else 1)))
+    return rng.integers(0, 256, (n, esz_of(dt)), dtype=np.uint8)
+
+
+def values_equal(dt: int, a, b) -> np.ndarray:
+    """Per lane: a == b as VALUES of dt (+0 == -0, NaN != NaN)."""
+    nd = oracle.DT_NP[dt]
+    a, b = np.ascontiguousarray(a).reshape(-1), np.ascontiguousarray(b).reshape(-1)
+    if nd.kind in "fc":
+        return a.view(nd) == b.view(nd)
+    return (a.reshape(-1, nd.itemsize) == b.reshape(-1, nd.itemsize)).all(axis=1)
+
+
+def _less(dt: int, a, b) -> np.ndarray:
+    """Per lane: a < b.  int128 / uint128 as (high, low) 64-bit words, the
+    high word signed for INT128."""
+    nd = oracle.DT_NP[dt]
+    a, b = np.ascontiguousarray(a).reshape(-1), np.ascontiguousarray(b).reshape(-1)
+    if nd.kind != "V":
+        return a.view(nd) < b.view(nd)
+    wa, wb = a.view(np.uint64).reshape(-1, 2), b.view(np.uint64).reshape(-1, 2)
+    ha, hb = wa[:, 1], wb[:, 1]
+    if _signed(dt):
+        ha, hb = ha.view(np.int64), hb.view(np.int64)
+    return (ha < hb) | ((ha == hb) & (wa[:, 0] < wb[:, 0]))
+
+
+SWAP_EDGE_PAIRS = ("+0,-0", "-0,+0", "nan,same nan", "nan,-nan", "1,nan", "nan,1", "inf,inf",
+                   "-inf,inf", "subnormal,0")
+
+
+def swap_edge_pairs(dt: int):
+    """The edge lanes' (dst, cmp) as two (k, esz) byte arrays.  Float types,
+    SWAP_EDGE_PAIRS in order (complex: the pair in both components): the +-0
+    pairs and the same-NaN pair separate a compare of bits from one of
+    values, the rest are the unordered and the infinite compares.  Integers:
+    (min, max), (max, min), (min, min), (-1, 0)."""
+    esz = esz_of(dt)
+    if is_float(dt):
+        ft = np.dtype(np.float32) if is_complex(dt) else oracle.DT_NP[dt]
+        sub = np.finfo(ft).smallest_subnormal
+        d = np.array([0.0, -0.0, np.nan, np.nan, 1.0, np.nan, np.inf, -np.inf, sub], ft)
+        c = np.array([-0.0, 0.0, np.nan, -np.nan, np.nan, 1.0, np.inf, np.inf, 0.0], ft)
+        if is_complex(dt):
+            d, c = np.repeat(d, 2), np.repeat(c, 2)
+        return d.view(np.uint8).reshape(-1, esz).copy(), c.view(np.uint8).reshape(-1, esz).copy()
+    bits = 8 * esz
+    lo, hi = (-(1 << (bits - 1)), (1 << (bits - 1)) - 1) if _signed(dt) else (0, (1 << bits) - 1)
+
+    def enc(vals):
+        return np.array([list((v % (1 << bits)).to_bytes(esz, "little")) for v in vals], np.uint8)
+    pairs = [(lo, hi), (hi, lo), (lo, lo), (-1, 0)]
+    return enc([p[0] for p in pairs]), enc([p[1] for p in pairs])
+
+
+def swap_inputs(op: int, dt: int, n: int, rng):
+    """dst, src, cmp of n elements (byte arrays) for a compare-table entry.
+
+    The CSWAP family: per lane two values a != b of the type and a class
+    drawn uniformly from {equal: cmp = dst = a; below: cmp = min, dst = max;
+    above: cmp = max, dst = min} (complex, which has no order: equal, and
+    differ twice), so every compare holds on 1/3 or 2/3 of the lanes and both
+    outcomes of an ordered compare are reached on purpose.  src differs from
+    dst in bits on every lane: a swap taken and a swap skipped always differ.
+    MSWAP: uniform bytes.  The last 64 lanes hold swap_edge_pairs."""
+    esz = esz_of(dt)
+    if op == MSWAP:
+        dst, src, cmp = (rng.integers(0, 256, (n, esz), dtype=np.uint8) for _ in range(3))
+    else:
+        a, b = _draw(dt, n, rng), _draw(dt, n, rng)
+        same = values_equal(dt, a, b)
+        while same.any():
+            b[same] = _draw(dt, int(same.sum()), rng)
+            same = values_equal(dt, a, b)
+        cls = rng.integers(0, 3, n)[:, None]
+        if is_complex(dt):
+            lo, hi = a, b
+        else:
+            lt = _less(dt, a, b)[:, None]
+            lo, hi = np.where(lt, a, b), np.where(lt, b, a)
+        dst = np.where(cls == 0, a, np.where(cls == 1, hi, lo))
+        cmp = np.where(cls == 0, a, np.where(cls == 1, lo, hi))
+        src = _draw(dt, n, rng)
+    ne = min(EDGE_LANES, n)
+    ed, ec = swap_edge_pairs(dt)
+    which = np.arange(ne) % ed.shape[0]
+    dst[n - ne:], cmp[n - ne:] = ed[which], ec[which]
+    if op != MSWAP:
+        src[(src == dst).all(axis=1), 0] ^= 1
+    return dst.reshape(-1), src.reshape(-1), cmp.reshape(-1)
+
+
+# ----------------------------------------------------------- table cases --
+
+class TableCase:
+    """One binary-table call's operands in one arena: the outputs (dst, res)
+    and the inputs.  `at`: operand name -> (start, bytes); `want`: the bytes
+    dst must hold afterwards, compared byte for byte where `exact` (nothing
+    is computed: the compare table, ATOMIC_READ), else through assert_same;
+    `odd`: the operand off the others' alignment, or None."""
+
+    def __init__(self, arena, at, want, exact, what, segs, path, odd):
+        self.arena, self.at, self.want, self.exact = arena, at, want, exact
+        self.what, self.segs, self.path, self.odd = what, segs, path, odd
+
+    def view(self, buf, name):
+        lo, nb = self.at[name]
+        return buf[lo:lo + nb]
+
+    def check(self, dt: int, got: np.ndarray) -> None:
+        got = np.asarray(got)
+        assert got.shape == self.arena.shape, self.what
+        assert L.gaps_intact(got, self.segs), f"{self.what}: a gap lost its sentinel"
+        for name in ("src", "cmp"):
+            if name in self.at:
+                assert np.array_equal(self.view(got, name), self.view(self.arena, name)), \
+                    f"{self.what}: {name} changed"
+        if "res" in self.at:        # a move: exact for every type
+            assert np.array_equal(self.view(got, "res"), self.view(self.arena, "dst")), \
+                f"{self.what}: res is not the old dst"
+        if self.exact:
+            assert np.array_equal(self.view(got, "dst"), self.want), f"{self.what}: dst"
+        else:
+            assert_same(dt, self.view(got, "dst").copy(), self.want, f"{self.what} dst")
+
+
+def carve_table(dt, names, data, want, exact, path, k=0, what=""):
+    """A TableCase for the operands `data` (name -> bytes; res, which has
+    none, holds OUT_FILL) in `names` order on `path`."""
+    esz = esz_of(dt)
+    n = lanes(esz)
+    assert n * esz == data["dst"].size
+    offs, odd = table_layout(esz, path, names, k)
+    segs, size = L.plan([n] * len(names), offs, esz)
+    arena = np.full(size, L.SENTINEL, np.uint8)
+    for name, (lo, nb) in zip(names, segs):
+        arena[lo:lo + nb] = data[name] if name in data else OUT_FILL
+    return TableCase(arena, dict(zip(names, segs)), want, exact,
+                     f"{what} {path}" + (f" odd={odd}" if odd else ""), segs, path, odd)
+
+
+def _on_paths(dt, names, data, want, exact, paths, turn, what):
+    for path in paths_of(esz_of(dt)):
+        if path in paths:
+            yield carve_table(dt, names, data, want, exact, path, turn[path], what)
+            turn[path] += 1
+
+
+def write_cases(op, dts, rng, paths=PATHS):
+    """Every case of lfa_atomic_write_async for one op: each type on each
+    path, the odd operand rotating from case to case."""
+    turn = dict.fromkeys(PATHS, 0)
+    for dt in dts:
+        d, s = inputs(SUM if op == WRITE else op, dt, 2, lanes(esz_of(dt)), rng)
+        yield from ((dt, c) for c in _on_paths(
+            dt, TABLE_OPERANDS["write"], {"dst": d, "src": s}, reference_write(op, dt, d, s),
+            False, paths, turn, f"write op={op} dt={dt}"))
+
+
+def readwrite_cases(op, dts, rng, paths=PATHS):
+    """Every case of lfa_atomic_readwrite_async for one op.  ATOMIC_READ has
+    no src: dst must come back as it was, byte for byte."""
+    turn = dict.fromkeys(PATHS, 0)
+    for dt in dts:
+        n = lanes(esz_of(dt))
+        if op == READ:
+            (d,) = inputs(SUM, dt, 1, n, rng)
+            names, data = TABLE_OPERANDS["read"], {"dst": d}
+            want = reference_readwrite(op, dt, d, None)
+        else:
+            d, s = inputs(SUM if op == WRITE else op, dt, 2, n, rng)
+            names, data = TABLE_OPERANDS["readwrite"], {"dst": d, "src": s}
+            want = reference_readwrite(op, dt, d, s)
+        yield from ((dt, c) for c in _on_paths(dt, names, data, want, op == READ, paths, turn,
+                                               f"readwrite op={op} dt={dt}"))
+
+
+def swap_cases(op, dts, rng, paths=PATHS):
+    """Every case of lfa_atomic_swap_async for one op."""
+    turn = dict.fromkeys(PATHS, 0)
+    for dt in dts:
+        d, s, c = swap_inputs(op, dt, lanes(esz_of(dt)), rng)
+        yield from ((dt, case) for case in _on_paths(
+            dt, TABLE_OPERANDS["swap"], {"dst": d, "src": s, "cmp": c},
+            reference_swap(op, dt, d, s, c), True, paths, turn, f"swap op={op} dt={dt}"))
+
+
+def operands_of(table: str, op: int):
+    return TABLE_OPERANDS["read" if table == "readwrite" and op == READ else table]
+
+
+def assert_every_operand_was_odd(table: str, op: int, cases) -> None:
+    """Over `cases` ((dt, TableCase) of one op of a table) every operand that
+    can take the odd offset on a path did so at least once; a fortiori over
+    the table."""
+    for path, cands in ODD.items():
+        seen = {c.odd for _, c in cases if c.path == path}
+        assert seen == {o for o in cands if o in operands_of(table, op)}, (table, op, path, seen)

@@ -362,7 +362,11 @@ def test_gpu_tree_any_fan_in(pair, nsrc, n, off, edge, seed):
        seed=st.integers(0, 2**31))
 def test_gpu_fetch_and_compare_any_shape(pair, n, off, edge, seed):
     """lfa_atomic_readwrite_async / lfa_atomic_swap_async against the oracle
-    (dst, src, cmp and res at one drawn byte offset)."""
+    (dst, src, cmp and res at one drawn byte offset).  Per-instantiation
+    coverage is tests/test_sweep_tables_gpu.py's to give: with one common
+    offset the not-co-aligned element kernel never runs here, an independent
+    cmp almost never equals dst off the copied lanes, and 120 draws do not
+    reach all 229 entries."""
     import torch
     from libfabric_amd import atomic
     op, dt = pair

@@ -11,7 +11,13 @@
 2. The layouts, the arena carving and the comparison code are right: the full
    case list of tests/test_sweep_gpu.py, run through the host combine
    (lfa_host_reduce_tree, lfa_host_writev) against the reference.
+3. The same for the three binary tables (tests/test_sweep_tables_gpu.py): the
+   pair lists, inputs under which a compare holds on 1/3 or 2/3 of the lanes
+   and a fetch changes dst, the edge pairs that separate a compare of bits from
+   one of values, and the full case list through lfa_host_write,
+   lfa_host_readwrite and lfa_host_swap.
 """
+import ctypes
 import json
 import os
 
@@ -19,9 +25,12 @@ import numpy as np
 import pytest
 
 from libfabric_amd import atomic
+from tests import _iov_layout as L
 from tests import _sweep as S
 
 OPS = range(10)
+TILE_VECS = L.TILE // 16    # 16-byte vectors per workgroup tile
+WAVE_VECS = 4 * 64          # per wave of it: 4 KiB
 SENS_LANES = 2600
 SENS_NSRC = (5, 32)
 MIN_CHANGED = 0.005
@@ -49,7 +58,10 @@ def test_pair_lists(manifest):
 
 def test_layouts_take_their_paths():
     """layout()'s offsets send lfa_split.h's rule down the path they name, at
-    every element size and operand count the sweep uses."""
+    every element size and operand count the sweep uses.  The one shape,
+    lanes(esz), gives launch_write and launch_fetch (16-KiB workgroup tiles
+    of 4 waves x 4 KiB, as the tree's widest body) two whole LDS tiles, a
+    partial tile with whole and partial waves, and a ragged tail."""
     for esz in (1, 2, 4, 8, 16):
         assert len(S.paths_of(esz)) == S.N_PATHS[esz]
         n = S.lanes(esz)
@@ -57,11 +69,26 @@ def test_layouts_take_their_paths():
         nvec = n * esz // 16
         # two whole 16-KiB workgroup tiles, a partial tile, a partial wave
         assert nvec // 1024 == 2 and nvec % 1024 and nvec % 64
+        # launch_write and launch_fetch cut the same 16-KiB tiles, 4 waves x
+        # 4 KiB (256 vectors): with or without an element head the partial
+        # tile holds whole wave tiles and a partial one, whose last 64-lane
+        # step is partial too
+        assert TILE_VECS == 4 * WAVE_VECS == 1024
+        for body in (nvec, (n * esz - (16 - esz)) // 16):      # vec path, head path
+            assert body // TILE_VECS == 2 and body % TILE_VECS // WAVE_VECS >= 1
+            assert body % WAVE_VECS and body % 64
+        assert n * esz % 16 or esz == 16                        # a ragged tail
         for path in S.paths_of(esz):
             for ndst, nsrc in [(1, k) for k in S.TREE_NSRC] + \
                     [(j, k) for j in S.PUT_NDST for k in S.PUT_NSRC]:
                 _, outs, ins = S.layout(esz, path, ndst, nsrc)
                 assert S.expect_path(esz, outs, ins) == path, (esz, path, ndst, nsrc)
+            # the binary tables' operands in launcher order, whoever is odd
+            for names in S.TABLE_OPERANDS.values():
+                for k in range(4):
+                    offs, odd = S.table_layout(esz, path, names, k)
+                    assert S.expect_path(esz, offs[:1], offs[1:]) == path
+                    assert (odd is not None) == (path in S.ODD)
     assert S.layout(4, "vec")[0] * 4 % 16          # a ragged tail
 
 
@@ -165,3 +192,192 @@ def test_check_sees_a_stray_write_and_a_changed_input():
         bad[at] ^= 0x10
         with pytest.raises(AssertionError):
             case.check(4, bad)
+
+
+# ------------------------------------------------------- binary tables ----
+
+SWAP_MIN_TAKEN, SWAP_MAX_TAKEN = 0.25, 0.75     # the class shares are 1/3 and 2/3
+MSWAP_MIN_CHANGED = 0.5
+RW_MIN_CHANGED = 0.25
+# cases per path as pairs with that path: every pair has vec; the 16-byte
+# types have neither head nor elem, the 1-byte types no bytes path
+N_WRITE_CASES = {"vec": 148, "head": 148 - 22, "elem": 148 - 22, "bytes": 148 - 22}
+N_RW_CASES = {"vec": 145, "head": 145 - 24, "elem": 145 - 24, "bytes": 145 - 24}
+N_SWAP_CASES = {"vec": 84, "head": 84 - 14, "elem": 84 - 14, "bytes": 84 - 14}
+
+
+def _table_entries(name, rows, first_op=0):
+    tbl = (ctypes.c_void_p * (rows * 16)).in_dll(atomic.lib(), name)
+    return {(first_op + i // 16, i % 16) for i in range(rows * 16) if tbl[i]}
+
+
+def test_table_pair_lists(manifest):
+    """145 fetch and 84 compare pairs: the oracle's, the golden manifest's
+    and the library's non-NULL table entries are one list; and the cases each
+    table's sweep runs per path."""
+    rp, sp, wp = S.rw_pairs(), S.swap_pairs(), S.write_pairs(manifest)
+    assert len(rp) == len(set(rp)) == S.N_RW_PAIRS == 145
+    assert len(sp) == len(set(sp)) == S.N_SWAP_PAIRS == 84
+    assert {(c["op"], c["dt"]) for c in manifest["readwrite"]} == set(rp)
+    assert {(c["op"], c["dt"]) for c in manifest["swap"]} == set(sp)
+    assert len(manifest["readwrite"]) == 145 and len(manifest["swap"]) == 84
+    assert _table_entries("lfa_atomic_readwrite_handlers", 12) == set(rp)
+    assert _table_entries("lfa_atomic_swap_handlers", 7, 12) == set(sp)
+    for op, dt in rp + sp:
+        assert atomic.datatype_size(dt) == S.esz_of(dt)
+    for pairs, per_path, total in ((wp, N_WRITE_CASES, 526), (rp, N_RW_CASES, 508),
+                                   (sp, N_SWAP_CASES, 294)):
+        for path in S.PATHS:
+            assert S.n_table_cases([dt for _, dt in pairs], (path,)) == per_path[path]
+        assert S.n_table_cases([dt for _, dt in pairs]) == sum(per_path.values()) == total
+
+
+def _taken(dt, old, new):
+    """Per lane: the reference changed dst (src differs from dst in bits on
+    every lane, so: the swap was taken)."""
+    e = S.esz_of(dt)
+    return (old.reshape(-1, e) != new.reshape(-1, e)).any(axis=1)
+
+
+@pytest.mark.parametrize("op", S.SWAP_OPS)
+def test_swap_inputs_are_informative(op):
+    """Under the reference alone: every compare holds on a share of the bulk
+    lanes in [0.25, 0.75]; each MSWAP operand decides dst on at least half."""
+    rng = np.random.default_rng(6000 + op)
+    dts = S.table_dts(S.swap_pairs(), op)
+    bulk = SENS_LANES - S.EDGE_LANES
+    for dt in dts:
+        d, s, c = S.swap_inputs(op, dt, SENS_LANES, rng)
+        want = S.reference_swap(op, dt, d, s, c)
+        if op != S.MSWAP:
+            e = S.esz_of(dt)
+            assert (d.reshape(-1, e) != s.reshape(-1, e)).any(axis=1).all(), (op, dt)
+            share = _taken(dt, d, want)[:bulk].mean()
+            assert SWAP_MIN_TAKEN <= share <= SWAP_MAX_TAKEN, (op, dt, share)
+            continue
+        for k in range(3):
+            other = [d, s, c]
+            other[k] = S.swap_inputs(op, dt, SENS_LANES, rng)[k]
+            changed = _taken(dt, want, S.reference_swap(op, dt, *other))[:bulk].mean()
+            assert changed >= MSWAP_MIN_CHANGED, (op, dt, k, changed)
+    assert len(dts) == {S.CSWAP: 13, S.CSWAP_NE: 13, S.MSWAP: 10}.get(op, 12)
+
+
+@pytest.mark.parametrize("dt", [8, 9, 10])
+def test_swap_edge_lanes_separate_bits_from_values(dt):
+    """FLOAT, DOUBLE, FLOAT_COMPLEX: every edge pair is among the last 64
+    lanes, and on the +-0 and the same-NaN lanes both CSWAP (bits: -0 is not
+    +0, a NaN is its own bits) and CSWAP_NE (values: -0 is +0, a NaN differs
+    from itself) answer the opposite of "cmp and dst are equal values", as
+    include/lfa_atomic.h states them."""
+    ft = np.dtype(np.float64) if dt == 9 else np.dtype(np.float32)
+    ub = np.uint64 if dt == 9 else np.uint32
+    step = 2 if dt == 10 else 1
+    sub = np.finfo(ft).smallest_subnormal
+    for op in (S.CSWAP, S.CSWAP_NE):
+        d, s, c = S.swap_inputs(op, dt, SENS_LANES, np.random.default_rng(6100 + op))
+        lo = (SENS_LANES - S.EDGE_LANES) * S.esz_of(dt)
+        dv, cv = d[lo:].view(ft)[::step], c[lo:].view(ft)[::step]
+        db, cb = d[lo:].view(ub)[::step], c[lo:].view(ub)[::step]
+        dneg, cneg = np.signbit(dv), np.signbit(cv)
+        zeros = (dv == 0) & (cv == 0) & (dneg != cneg)
+        same_nan = np.isnan(dv) & (db == cb)
+        present = {
+            "+0,-0": zeros & ~dneg, "-0,+0": zeros & dneg, "nan,same nan": same_nan,
+            "nan,-nan": np.isnan(dv) & np.isnan(cv) & (db != cb),
+            "1,nan": (dv == 1) & np.isnan(cv), "nan,1": np.isnan(dv) & (cv == 1),
+            "inf,inf": (dv == np.inf) & (cv == np.inf),
+            "-inf,inf": (dv == -np.inf) & (cv == np.inf),
+            "subnormal,0": (dv == sub) & (cv == 0) & ~cneg,
+        }
+        assert set(present) == set(S.SWAP_EDGE_PAIRS)
+        for name, lanes in present.items():
+            assert lanes.any(), (op, dt, name)
+        taken = _taken(dt, d, S.reference_swap(op, dt, d, s, c))[-S.EDGE_LANES:]
+        veq = S.values_equal(dt, c, d)[-S.EDGE_LANES:]
+        assert veq[zeros].all() and not veq[same_nan].any()
+        assert not taken[zeros].any() and taken[same_nan].all(), (op, dt)
+        assert (taken != veq)[zeros | same_nan].all(), (op, dt)
+
+
+@pytest.mark.parametrize("op", [op for op in S.RW_OPS if op != S.READ])
+def test_readwrite_inputs_are_informative(op):
+    """The reference's new dst differs from the old one on at least 25 % of
+    the bulk lanes: a kernel that wrote the new value to res, or left dst
+    alone, cannot pass."""
+    rng = np.random.default_rng(6200 + op)
+    dts = S.table_dts(S.rw_pairs(), op)
+    for dt in dts:
+        d, s = S.inputs(S.SUM if op == S.WRITE else op, dt, 2, SENS_LANES, rng)
+        changed = _taken(dt, d, S.reference_readwrite(op, dt, d, s))
+        share = changed[:SENS_LANES - S.EDGE_LANES].mean()
+        assert share >= RW_MIN_CHANGED, (op, dt, share)
+    assert dts
+
+
+@pytest.mark.parametrize("op", S.WRITE_OPS)
+def test_host_write_every_case(op, manifest):
+    """tests/test_sweep_tables_gpu.py's write cases through lfa_host_write."""
+    dts = S.table_dts(S.write_pairs(manifest), op)
+    cases = list(S.write_cases(op, dts, np.random.default_rng(7000 + op)))
+    for dt, case in cases:
+        a = case.arena.copy()
+        atomic.host_write(op, dt, case.view(a, "dst"), case.view(a, "src"),
+                          S.lanes(S.esz_of(dt)))
+        case.check(dt, a)
+    assert len(cases) == S.n_table_cases(dts) == sum(S.N_PATHS[S.esz_of(dt)] for dt in dts)
+    S.assert_every_operand_was_odd("write", op, cases)
+
+
+@pytest.mark.parametrize("op", S.RW_OPS)
+def test_host_readwrite_every_case(op):
+    dts = S.table_dts(S.rw_pairs(), op)
+    cases = list(S.readwrite_cases(op, dts, np.random.default_rng(8000 + op)))
+    for dt, case in cases:
+        a = case.arena.copy()
+        atomic.host_readwrite(op, dt, case.view(a, "dst"),
+                              case.view(a, "src") if "src" in case.at else None,
+                              case.view(a, "res"), S.lanes(S.esz_of(dt)))
+        case.check(dt, a)
+    assert len(cases) == S.n_table_cases(dts) == sum(S.N_PATHS[S.esz_of(dt)] for dt in dts)
+    S.assert_every_operand_was_odd("readwrite", op, cases)
+
+
+@pytest.mark.parametrize("op", S.SWAP_OPS)
+def test_host_swap_every_case(op):
+    dts = S.table_dts(S.swap_pairs(), op)
+    cases = list(S.swap_cases(op, dts, np.random.default_rng(9000 + op)))
+    for dt, case in cases:
+        a = case.arena.copy()
+        atomic.host_swap(op, dt, case.view(a, "dst"), case.view(a, "src"),
+                         case.view(a, "cmp"), case.view(a, "res"), S.lanes(S.esz_of(dt)))
+        case.check(dt, a)
+    assert len(cases) == S.n_table_cases(dts) == sum(S.N_PATHS[S.esz_of(dt)] for dt in dts)
+    S.assert_every_operand_was_odd("swap", op, cases)
+
+
+def test_table_check_sees_its_faults():
+    """TableCase.check itself, on a compare and on a fetch case: a byte in a
+    gap, a changed src, a changed cmp, res holding the new value, one wrong
+    lane of dst."""
+    rng = np.random.default_rng(8)
+    (_, sw), = S.swap_cases(S.CSWAP_LE, [4], rng, paths=("vec",))
+    (_, rw), = S.readwrite_cases(S.SUM, [8], rng, paths=("head",))
+    for dt, case in ((4, sw), (8, rw)):
+        good = case.arena.copy()
+        case.view(good, "res")[:] = case.view(case.arena, "dst")
+        case.view(good, "dst")[:] = case.want
+        case.check(dt, good)
+        faults = {"gap": case.at["dst"][0] - 1, "src": case.at["src"][0] + 5,
+                  "dst lane": case.at["dst"][0] + 4 * 9 + 2}
+        if "cmp" in case.at:
+            faults["cmp"] = case.at["cmp"][0] + case.at["cmp"][1] - 1
+        for what, at in faults.items():
+            bad = good.copy()
+            bad[at] ^= 0x10
+            with pytest.raises(AssertionError):
+                case.check(dt, bad)
+        bad = good.copy()
+        case.view(bad, "res")[:] = case.want
+        with pytest.raises(AssertionError, match="res is not the old dst"):
+            case.check(dt, bad)
