@@ -481,8 +481,10 @@ struct lfa_step {
  * `esz` bytes in an `nranks` group (root: group rank, or -1).  Writes up to
  * *nsteps steps / *nrefs refs and returns the counts in them, and the HBM
  * workspace the schedule needs in *tmp_bytes.  Host-only, no GPU needed.
- * Returns 0, -LFA_EINVAL, -LFA_ENOSYS (collective/algo not planned) or
- * -LFA_ETOOSMALL (arrays too short; *nsteps and *nrefs = sizes needed).
+ * Returns 0, -LFA_EINVAL, -LFA_ENOSYS (collective/algo not planned),
+ * -LFA_ETOOSMALL (arrays too short; *nsteps and *nrefs = sizes needed) or
+ * -LFA_ENOMEM (the schedule is built in memory of the call's own, a size
+ * query's too, and copied out).
  */
 #define LFA_ETOOSMALL 257
 int lfa_coll_plan(enum lfa_collective_op coll, enum lfa_coll_algo algo,

@@ -65,15 +65,16 @@ LFA_INTERNAL int run_local(const struct lfa_step *s, const struct lfa_ref *refs,
 	case LFA_STEP_TREE_PUT: {
 		const void *srcs[LFA_TREE_MAX];
 		void *dsts[LFA_PUT_MAX];
+		const int extra = lfa_step_put_extra(s);
 
-		if (s->nsrc > LFA_TREE_MAX || s->peer < 0 || s->peer + 1 > LFA_PUT_MAX)
+		if (s->nsrc > LFA_TREE_MAX || extra < 0 || extra + 1 > LFA_PUT_MAX)
 			return -LFA_EINVAL;
 		for (uint32_t k = 0; k < s->nsrc; k++)
 			srcs[k] = resolve(x, refs[s->first + k]);
 		dsts[0] = resolve(x, s->dst);
-		for (int j = 0; j < s->peer; j++)
+		for (int j = 0; j < extra; j++)
 			dsts[1 + j] = resolve(x, refs[s->first + s->nsrc + (uint32_t)j]);
-		return lfa_reduce_tree_put_async(op, dt, dsts, 1 + s->peer, srcs,
+		return lfa_reduce_tree_put_async(op, dt, dsts, 1 + extra, srcs,
 						 (int)s->nsrc, s->count, stream);
 	}
 	case LFA_STEP_COPY:
@@ -113,45 +114,6 @@ LFA_INTERNAL int run_local(const struct lfa_step *s, const struct lfa_ref *refs,
 		return -LFA_EINVAL;
 	}
 }
-
-/* Does the plan address the symmetric workspace? */
-LFA_INTERNAL int plan_uses_sym(const struct lfa_step *st, size_t nsteps)
-{
-	for (size_t i = 0; i < nsteps; i++)
-		if (st[i].type == LFA_STEP_BARRIER || st[i].type == LFA_STEP_TREE_PUT ||
-		    st[i].type == LFA_STEP_ONESHOT)
-			return 1;
-	return 0;
-}
-
-/* Bytes of one symmetric-workspace region for `count` elements. */
-LFA_INTERNAL size_t sym_region(size_t count, size_t esz)
-{
-	return (count * esz + 255) & ~(size_t)255;
-}
-
-/* One ONESHOT slot: the largest part any member reduces. */
-static size_t os_slot(const struct lfa_step *st, int n, size_t esz)
-{
-	size_t part = st->count;
-
-	if (st->peer == LFA_ONESHOT_SCATTER)
-		part = (st->count + (size_t)n - 1) / (size_t)n;
-	return sym_region(part, esz);
-}
-
-LFA_INTERNAL size_t plan_sym_need(const struct lfa_step *st, size_t nsteps, int n,
-				  size_t count, size_t esz)
-{
-	size_t need = sym_region(count, esz);
-
-	for (size_t i = 0; i < nsteps; i++)
-		if (st[i].type == LFA_STEP_ONESHOT &&
-		    2 * (size_t)n * os_slot(&st[i], n, esz) > need)
-			need = 2 * (size_t)n * os_slot(&st[i], n, esz);
-	return need;
-}
-
 
 /* How long a flag barrier waits for a member before failing the operation
  * (LFA_SIG_TIMEOUT_MS, default 20 s). */
@@ -211,9 +173,9 @@ LFA_INTERNAL int sig_oneshot(struct xrun *r, const struct lfa_step *st)
 	memset(&a, 0, sizeof(a));
 	a.send = resolve(&r->x, st->src);
 	/* reduce: a non-root has no result */
-	a.result = st->peer >= 0 && st->peer != mc->rank ? NULL : resolve(&r->x, st->dst);
+	a.result = lfa_oneshot_has_result(st, mc->rank) ? resolve(&r->x, st->dst) : NULL;
 	a.count = st->count;
-	a.mode = st->peer;
+	a.mode = lfa_oneshot_mode(st);
 	a.sym = r->x.sym;
 	a.slot_bytes = os_slot(st, mc->size, esz);
 	a.parity_off = (r->x.region / 2) & ~(size_t)255;   /* the same on every member */

@@ -502,11 +502,6 @@ LFA_INTERNAL void *resolve(const struct xctx *x, struct lfa_ref r);
 LFA_INTERNAL int run_local(const struct lfa_step *s, const struct lfa_ref *refs,
 			   const struct xctx *x, enum lfa_op op, enum lfa_datatype dt,
 			   hipStream_t stream);
-LFA_INTERNAL int plan_uses_sym(const struct lfa_step *st, size_t nsteps);
-LFA_INTERNAL size_t sym_region(size_t count, size_t esz);
-/* Bytes per workspace region the plan needs (ONESHOT: 2·n slots). */
-LFA_INTERNAL size_t plan_sym_need(const struct lfa_step *st, size_t nsteps, int n,
-				  size_t count, size_t esz);
 LFA_INTERNAL int xrun_advance(struct xrun *r);
 /* BARRIER of a plan on the symmetric workspace: the flag-barrier kernel. */
 LFA_INTERNAL int sig_barrier(struct xrun *r);

@@ -1,8 +1,9 @@
 /*
  * lfa_coll_plan.h — internal interface between the schedule builder
- * (lfa_coll_plan.c) and the executor (lfa_coll.c, lfa_coll_exec.c,
- * lfa_coll_loopback.c) of liblfa_coll.so.  Not
- * installed; nothing here is exported from the library.
+ * (lfa_coll_plan.c: plans, their lowering, the queries on a finished plan)
+ * and the code of liblfa_coll.so that submits and runs plans (lfa_coll.c,
+ * lfa_coll_host.c, lfa_coll_exec.c, lfa_coll_loopback.c).  Not installed;
+ * nothing here is exported from the library.
  */
 #ifndef LFA_COLL_PLAN_H
 #define LFA_COLL_PLAN_H
@@ -53,6 +54,38 @@ static inline int coll_reduces(enum lfa_collective_op coll)
 	return coll == LFA_ALLREDUCE || coll == LFA_REDUCE || coll == LFA_REDUCE_SCATTER;
 }
 
+/* ---- lfa_step.peer off SEND/RECV (include/lfa_coll.h documents the
+ *      encoding; these name it) ------------------------------------------ */
+
+/* TREE_PUT: destinations beside dst, refs[first + nsrc ..). */
+static inline int lfa_step_put_extra(const struct lfa_step *st)
+{
+	return st->peer;
+}
+
+/* ONESHOT: LFA_ONESHOT_ALL, LFA_ONESHOT_SCATTER, or the root of a reduce. */
+static inline int lfa_oneshot_mode(const struct lfa_step *st)
+{
+	return st->peer;
+}
+
+/* ONESHOT: does group rank r end with a result (reduce: the root only)? */
+static inline int lfa_oneshot_has_result(const struct lfa_step *st, int r)
+{
+	return st->peer < 0 || st->peer == r;
+}
+
+/* ONESHOT: the elements [off, off + len) rank r of n reduces: its block
+ * (SCATTER), everything, or nothing off a reduce's root. */
+static inline void lfa_oneshot_part(const struct lfa_step *st, int n, int r,
+				    size_t *off, size_t *len)
+{
+	*off = 0;
+	*len = lfa_oneshot_has_result(st, r) ? st->count : 0;
+	if (st->peer == LFA_ONESHOT_SCATTER)
+		lfa_coll_block(st->count, n, r, off, len);
+}
+
 /* A heap-allocated plan. */
 struct plan {
 	struct lfa_step *steps;
@@ -61,7 +94,7 @@ struct plan {
 };
 
 LFA_INTERNAL void plan_free(struct plan *pl);
-/* lfa_coll_plan into freshly allocated arrays */
+/* lfa_coll_plan into arrays of the plan's own */
 LFA_INTERNAL int plan_make(struct plan *pl, enum lfa_collective_op coll,
 			   enum lfa_coll_algo algo, int rank, int n, int root,
 			   size_t count, size_t esz);
@@ -69,5 +102,17 @@ LFA_INTERNAL int plan_make(struct plan *pl, enum lfa_collective_op coll,
  * lower_oneshot: ONESHOT -> COPY, BARRIER, TREE, BARRIER */
 LFA_INTERNAL int lower_plan(const struct plan *in, int r, int n, size_t esz,
 			    struct plan *out, int lower_barrier, int lower_oneshot);
+
+/* ---- plan queries ----------------------------------------------------- */
+
+/* Does the plan address the symmetric workspace? */
+LFA_INTERNAL int plan_uses_sym(const struct lfa_step *st, size_t nsteps);
+/* Bytes of one symmetric-workspace region for `count` elements. */
+LFA_INTERNAL size_t sym_region(size_t count, size_t esz);
+/* One ONESHOT slot: the largest part any member reduces. */
+LFA_INTERNAL size_t os_slot(const struct lfa_step *st, int n, size_t esz);
+/* Bytes per workspace region the plan needs (ONESHOT: 2·n slots). */
+LFA_INTERNAL size_t plan_sym_need(const struct lfa_step *st, size_t nsteps, int n,
+				  size_t count, size_t esz);
 
 #endif
