@@ -218,6 +218,48 @@ int lfa_atomic_swap_async(enum lfa_op op, enum lfa_datatype datatype,
 			  void *res, size_t cnt, void *stream);
 
 /*
+ * The list forms of the fetch and compare tables: what fi_fetch_atomicv /
+ * fi_fetch_atomicmsg and fi_compare_atomicv / fi_compare_atomicmsg hand a
+ * provider, combined in ONE launch.  For every segment i and j < dst[i].count
+ *     res[i].addr[j] = dst[i].addr[j], then dst[i].addr[j] is updated
+ * — bit for bit what one lfa_atomic_readwrite_async / lfa_atomic_swap_async
+ * per segment gives (LFA_CSWAP compares bits).
+ * Pairs: those lfa_atomic_valid(datatype, op, LFA_FETCH_ATOMIC) /
+ * (..., LFA_COMPARE_ATOMIC) accept; no 16-bit float forms, as in the
+ * contiguous calls.  Under LFA_ATOMIC_READ the src list is not looked at: it
+ * may be NULL or hold NULL addresses.
+ * Segments, empty segments, nseg == 0, the caller's arrays, the ring and graph
+ * capture: exactly as lfa_atomic_writev_async above.  Every segment takes the
+ * vector, element or byte-wise path that ALL of its operands (dst, src, cmp,
+ * res) permit.  A table travels in the kernel arguments (and the call may be
+ * captured) up to 14 readwritev segments (records of dst, count, src, res) and
+ * up to 11 swapv segments (dst, count, src, cmp, res); one non-empty segment
+ * is forwarded to the contiguous call and needs no table at all.
+ * Overlap: dst AND res are written, so all non-empty dst[i] and res[i] ranges
+ * of a call must be pairwise disjoint — res[i] against dst[i], against dst[j]
+ * and against res[j]; ranges that only touch are fine.  As with writev, only
+ * written ranges are checked: a src[i] or cmp[i] must not overlap dst[j] or
+ * res[j] for j != i; the result of such a list is undefined and no error is
+ * reported.
+ * Errors, all reported before anything is enqueued, by one check the device
+ * and host forms share:
+ *   -LFA_EOPNOTSUPP  lfa_atomic_valid refuses (datatype, op) for the table
+ *   -LFA_EINVAL      a NULL array (except src under LFA_ATOMIC_READ); a NULL
+ *                    addr with a non-zero count; an operand's count differing
+ *                    from dst[i].count; nseg > LFA_IOV_MAX; two written
+ *                    ranges sharing a byte
+ *   -LFA_EIO         a HIP failure
+ *   -LFA_ENOMEM      a ring slot could not be allocated or grown
+ */
+int lfa_atomic_readwritev_async(enum lfa_op op, enum lfa_datatype datatype,
+				const struct lfa_ioc *dst, const struct lfa_ioc *src,
+				const struct lfa_ioc *res, size_t nseg, void *stream);
+int lfa_atomic_swapv_async(enum lfa_op op, enum lfa_datatype datatype,
+			   const struct lfa_ioc *dst, const struct lfa_ioc *src,
+			   const struct lfa_ioc *cmp, const struct lfa_ioc *res,
+			   size_t nseg, void *stream);
+
+/*
  * Host-resident buffers (what prov/coll's REDUCE items see, coll_coll.c:763):
  * dst/src are streamed through HBM in `chunk_bytes` pieces (0 = 32 MiB) on
  * two HIP streams — chunk c+1's H2D overlaps chunk c's combine and D2H — and
@@ -260,6 +302,15 @@ int lfa_host_readwrite(enum lfa_op op, enum lfa_datatype datatype, void *dst,
 		       const void *src, void *res, size_t cnt);
 int lfa_host_swap(enum lfa_op op, enum lfa_datatype datatype, void *dst,
 		  const void *src, const void *cmp, void *res, size_t cnt);
+/* lfa_host_readwritev / lfa_host_swapv: the list forms on host memory, what
+ * nseg calls of lfa_host_readwrite / lfa_host_swap give; arguments and errors
+ * as lfa_atomic_readwritev_async / lfa_atomic_swapv_async. */
+int lfa_host_readwritev(enum lfa_op op, enum lfa_datatype datatype,
+			const struct lfa_ioc *dst, const struct lfa_ioc *src,
+			const struct lfa_ioc *res, size_t nseg);
+int lfa_host_swapv(enum lfa_op op, enum lfa_datatype datatype,
+		   const struct lfa_ioc *dst, const struct lfa_ioc *src,
+		   const struct lfa_ioc *cmp, const struct lfa_ioc *res, size_t nseg);
 
 /*
  * The synchronous tables (lfa_atomic_write_handlers and the fetch / compare

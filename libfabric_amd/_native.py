@@ -86,6 +86,16 @@ def _bind_lfa(L):
     L.lfa_host_swap.restype = c_int
     L.lfa_host_swap.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_size_t]
+    L.lfa_atomic_readwritev_async.restype = c_int
+    L.lfa_atomic_readwritev_async.argtypes = [c_int, c_int, ioc_p, ioc_p, ioc_p, c_size_t,
+                                              c_void_p]
+    L.lfa_atomic_swapv_async.restype = c_int
+    L.lfa_atomic_swapv_async.argtypes = [c_int, c_int, ioc_p, ioc_p, ioc_p, ioc_p, c_size_t,
+                                         c_void_p]
+    L.lfa_host_readwritev.restype = c_int
+    L.lfa_host_readwritev.argtypes = [c_int, c_int, ioc_p, ioc_p, ioc_p, c_size_t]
+    L.lfa_host_swapv.restype = c_int
+    L.lfa_host_swapv.argtypes = [c_int, c_int, ioc_p, ioc_p, ioc_p, ioc_p, c_size_t]
 
 
 def _bind_tune(L):

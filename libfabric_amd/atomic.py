@@ -12,6 +12,9 @@ Mirrors the reference's L4 combine interface (include/ofi_atomic.h:45-90):
   writev / reduce_treev / host_writev  the fi_ioc (list) forms of write /
                                     reduce_tree / host_write: every segment of
                                     a list in one launch (fi_atomicv's shape)
+  readwritev / swapv / host_readwritev / host_swapv  the same for the fetch
+                                    and compare tables (fi_fetch_atomicv,
+                                    fi_compare_atomicv)
   host_readwrite / host_swap        the fetch and compare tables on host
                                     buffers (lfa_host_readwrite / lfa_host_swap)
   reduce_valid / reduce_datatype_size  what write / reduce_tree / the
@@ -247,6 +250,69 @@ def host_writev(op: int, dt: int, dsts, srcs) -> None:
     rc = lib().lfa_host_writev(int(op), int(dt), da, sa, len(dsts))
     if rc:
         raise LfaError(rc, f"lfa_host_writev({op},{dt})")
+
+
+def _fetch_lists(dt: int, ptr, dsts, **others):
+    """The lfa_ioc arrays of a fetch / compare list call: dsts, then every
+    list of `others` in order (None stays None: ATOMIC_READ's srcs)."""
+    esz = datatype_size(dt)
+    out = []
+    for name, lst in (("dsts", dsts), *others.items()):
+        if lst is None:
+            out.append(None)
+            continue
+        if len(lst) != len(dsts):
+            raise ValueError(f"dsts and {name} differ in length")
+        out.append(_ioc_array([ptr(t, f"{name}[{i}]") for i, t in enumerate(lst)],
+                              _seg_counts(lst, esz) if esz else []))
+    return out
+
+
+def _dev_ptr(t: torch.Tensor, name: str) -> int:
+    _check_dev(t, name)
+    return t.data_ptr()
+
+
+def readwritev(op: int, dt: int, dsts: list[torch.Tensor], srcs: list[torch.Tensor] | None,
+               ress: list[torch.Tensor], stream=None) -> None:
+    """ress[i] = dsts[i]; dsts[i] = dsts[i] OP srcs[i] for every i in ONE launch
+    (lfa_atomic_readwritev_async, the fi_ioc form of ``readwrite``).
+    ATOMIC_READ ignores srcs, which may be None."""
+    da, sa, ra = _fetch_lists(dt, _dev_ptr, dsts, srcs=srcs, ress=ress)
+    rc = lib().lfa_atomic_readwritev_async(int(op), int(dt), da, sa, ra, len(dsts),
+                                           _stream_handle(stream))
+    if rc:
+        raise LfaError(rc, f"lfa_atomic_readwritev_async({op},{dt})")
+
+
+def swapv(op: int, dt: int, dsts: list[torch.Tensor], srcs: list[torch.Tensor],
+          cmps: list[torch.Tensor], ress: list[torch.Tensor], stream=None) -> None:
+    """ress[i] = dsts[i]; dsts[i] = srcs[i] where (cmps[i] OP dsts[i]) for every
+    i in ONE launch (lfa_atomic_swapv_async, the fi_ioc form of ``swap``)."""
+    da, sa, ca, ra = _fetch_lists(dt, _dev_ptr, dsts, srcs=srcs, cmps=cmps, ress=ress)
+    rc = lib().lfa_atomic_swapv_async(int(op), int(dt), da, sa, ca, ra, len(dsts),
+                                      _stream_handle(stream))
+    if rc:
+        raise LfaError(rc, f"lfa_atomic_swapv_async({op},{dt})")
+
+
+def host_readwritev(op: int, dt: int, dsts, srcs, ress) -> None:
+    """``readwritev`` on HOST buffers (numpy arrays or CPU tensors):
+    lfa_host_readwritev, what one host_readwrite per segment gives."""
+    da, sa, ra = _fetch_lists(dt, lambda a, _: _host_ptr(a), dsts, srcs=srcs, ress=ress)
+    rc = lib().lfa_host_readwritev(int(op), int(dt), da, sa, ra, len(dsts))
+    if rc:
+        raise LfaError(rc, f"lfa_host_readwritev({op},{dt})")
+
+
+def host_swapv(op: int, dt: int, dsts, srcs, cmps, ress) -> None:
+    """``swapv`` on HOST buffers: lfa_host_swapv, what one host_swap per
+    segment gives."""
+    da, sa, ca, ra = _fetch_lists(dt, lambda a, _: _host_ptr(a), dsts, srcs=srcs, cmps=cmps,
+                                  ress=ress)
+    rc = lib().lfa_host_swapv(int(op), int(dt), da, sa, ca, ra, len(dsts))
+    if rc:
+        raise LfaError(rc, f"lfa_host_swapv({op},{dt})")
 
 
 # ------------------------------------------------------- host-memory forms --

@@ -24,8 +24,8 @@
 //   fetch_lds/elem the fetch (readwrite) and compare-swap tables
 //                  (util_atomic.c:924-980): res = old dst, then the update;
 //                  fetch_lds and fetch_lds_taper over one tile body, fetch_tile.
-//   combine_iov, reduce_iov  the list (fi_ioc) forms: every segment of a call
-//                  in one launch (lfa_k_iov.hpp).
+//   combine_iov, reduce_iov, fetch_iov  the list (fi_ioc) forms: every segment
+//                  of a call in one launch (lfa_k_iov.hpp).
 //
 // Kernels and launchers: lfa_kernels.hpp (how a buffer is cut into head,
 // vectors and tail: lfa_split.h).  The forms only the tuning library builds:
@@ -122,6 +122,26 @@ static int by_iov_type(int dt, F &&f) {
   }
 }
 
+// The fetch and compare list forms: ATOMIC_READ and ATOMIC_WRITE (an exchange)
+// only move bytes, so they run the unsigned integer of the element's width
+// whatever the datatype; every other op shares as the contiguous tables do.
+template <int OP, typename F>
+static int by_iov_fetch_type(int dt, F &&f) {
+  if constexpr (OP == OP_READ || OP == OP_WRITE) {
+    if ((unsigned)dt >= LFA_DATATYPE_CNT) return -LFA_EOPNOTSUPP;
+    switch (lfa_datatype_size((lfa_datatype)dt)) {
+      case 1: return f((uint8_t *)0);
+      case 2: return f((uint16_t *)0);
+      case 4: return f((uint32_t *)0);
+      case 8: return f((uint64_t *)0);
+      case 16: return f((u128 *)0);
+      default: return -LFA_EOPNOTSUPP;
+    }
+  } else {
+    return by_type<OP>(dt, f);
+  }
+}
+
 }  // namespace lfa
 
 #ifndef LFA_OP
@@ -203,9 +223,17 @@ static int op_readwrite(int dt, void *dst, const void *src, void *res, size_t cn
                                             (hipStream_t)stream);
   });
 }
+static int op_readwritev(int dt, const lfa_iov_args *a, unsigned ntile, void *stream) {
+  return lfa::by_iov_fetch_type<LFA_OP>(dt, [&](auto *tag) {
+    typedef typename std::remove_pointer<decltype(tag)>::type T;
+    return lfa::launch_readwritev<LFA_OP, T>(*a, ntile, (hipStream_t)stream);
+  });
+}
 constexpr lfa_launch_swap_t op_swap = nullptr;
+constexpr lfa_launch_fetchv_t op_swapv = nullptr;
 #else
 constexpr lfa_launch_readwrite_t op_readwrite = nullptr;
+constexpr lfa_launch_fetchv_t op_readwritev = nullptr;
 static int op_swap(int dt, void *dst, const void *src, const void *cmp, void *res,
                    size_t cnt, void *stream) {
   return lfa::by_type<LFA_OP>(dt, [&](auto *tag) {
@@ -214,10 +242,18 @@ static int op_swap(int dt, void *dst, const void *src, const void *cmp, void *re
                                        (hipStream_t)stream);
   });
 }
+
+static int op_swapv(int dt, const lfa_iov_args *a, unsigned ntile, void *stream) {
+  return lfa::by_type<LFA_OP>(dt, [&](auto *tag) {
+    typedef typename std::remove_pointer<decltype(tag)>::type T;
+    return lfa::launch_swapv<LFA_OP, T>(*a, ntile, (hipStream_t)stream);
+  });
+}
 #endif
 
 // host data: the device pass would emit a const object too, and has no entries
 #ifndef __HIP_DEVICE_COMPILE__
 extern "C" const lfa_op_launch LFA_CAT(lfa__op, LFA_OP) = {
-    op_write, op_writev, op_tree, op_treev, op_treeput, op_oneshot, op_readwrite, op_swap};
+    op_write,   op_writev,    op_tree, op_treev,      op_treeput,
+    op_oneshot, op_readwrite, op_swap, op_readwritev, op_swapv};
 #endif

@@ -258,29 +258,28 @@ int lfa_host_reduce_tree(enum lfa_op op, enum lfa_datatype dt, void *dst,
   });
 }
 
-// The list forms' argument check, shared by lfa_host_writev and the device
-// forms of lfa_iov.cpp: everything that makes a call -LFA_EINVAL, found
-// before any element is touched.  `src` may be null (lfa_reduce_treev_async
-// has no src list).  Two dst segments must not share a byte: separate calls
-// would order them, one launch cannot.  The ranges are sorted by start
-// (O(nseg log nseg)) and each start is compared with the end of the range
-// before it; the scan stops at the first overlap, so up to there that end is
-// also the furthest end seen.  Only dst ranges are compared: an input that
-// overlaps another segment's dst is the caller's to avoid (lfa_atomic.h).
-int lfa__iov_check(const struct lfa_ioc *dst, const struct lfa_ioc *src, int has_src,
-                   size_t nseg, size_t esz) {
-  if (nseg > LFA_IOV_MAX || !dst || (has_src && !src) || !esz) return -LFA_EINVAL;
-  static thread_local std::vector<std::pair<uintptr_t, uintptr_t>> range;
-  range.clear();
-  for (size_t i = 0; i < nseg; i++) {
-    const size_t n = dst[i].count;
-    if (has_src && src[i].count != n) return -LFA_EINVAL;
-    if (!n) continue;
-    if (!dst[i].addr || (has_src && !src[i].addr)) return -LFA_EINVAL;
-    const uintptr_t lo = (uintptr_t)dst[i].addr;
-    if (n > SIZE_MAX / esz || lo + n * esz < lo) return -LFA_EINVAL;
-    range.emplace_back(lo, lo + n * esz);
-  }
+// The list forms' argument check, shared by the host forms below and the
+// device forms of lfa_iov.cpp: everything that makes a call -LFA_EINVAL, found
+// before any element is touched.  Two written segments must not share a byte:
+// separate calls would order them, one launch cannot.  The written ranges
+// (dst, and res for the fetch and compare forms) are sorted by start
+// (O(n log n)) and each start is compared with the end of the range before it;
+// the scan stops at the first overlap, so up to there that end is also the
+// furthest end seen.  Only written ranges are compared: an input that overlaps
+// another segment's written range is the caller's to avoid (lfa_atomic.h).
+namespace {
+
+typedef std::vector<std::pair<uintptr_t, uintptr_t>> IovRanges;
+
+// a written operand's non-empty range joins `range`; false: NULL or wrapping
+bool iov_written(IovRanges &range, const void *addr, size_t n, size_t esz) {
+  const uintptr_t lo = (uintptr_t)addr;
+  if (!addr || n > SIZE_MAX / esz || lo + n * esz < lo) return false;
+  range.emplace_back(lo, lo + n * esz);
+  return true;
+}
+
+int iov_disjoint(IovRanges &range) {
   std::sort(range.begin(), range.end());
   uintptr_t end = 0;
   for (const auto &r : range) {
@@ -290,6 +289,49 @@ int lfa__iov_check(const struct lfa_ioc *dst, const struct lfa_ioc *src, int has
   return 0;
 }
 
+thread_local IovRanges t_iov_range;
+
+}  // namespace
+
+// dst and, unless !has_src (lfa_reduce_treev_async has no src list), src.
+int lfa__iov_check(const struct lfa_ioc *dst, const struct lfa_ioc *src, int has_src,
+                   size_t nseg, size_t esz) {
+  if (nseg > LFA_IOV_MAX || !dst || (has_src && !src) || !esz) return -LFA_EINVAL;
+  IovRanges &range = t_iov_range;
+  range.clear();
+  for (size_t i = 0; i < nseg; i++) {
+    const size_t n = dst[i].count;
+    if (has_src && src[i].count != n) return -LFA_EINVAL;
+    if (!n) continue;
+    if (has_src && !src[i].addr) return -LFA_EINVAL;
+    if (!iov_written(range, dst[i].addr, n, esz)) return -LFA_EINVAL;
+  }
+  return iov_disjoint(range);
+}
+
+// The fetch (cmp == NULL, !has_cmp) and compare forms: dst and res are both
+// written, so the 2 * nseg ranges of dst and res must be pairwise disjoint —
+// res[i] against dst[i] and against every other segment's dst and res.
+// !has_src (ATOMIC_READ): the src list is not looked at, it may be NULL.
+int lfa__iov_fetch_check(const struct lfa_ioc *dst, const struct lfa_ioc *src, int has_src,
+                         const struct lfa_ioc *cmp, int has_cmp, const struct lfa_ioc *res,
+                         size_t nseg, size_t esz) {
+  if (nseg > LFA_IOV_MAX || !dst || !res || (has_src && !src) || (has_cmp && !cmp) || !esz)
+    return -LFA_EINVAL;
+  IovRanges &range = t_iov_range;
+  range.clear();
+  for (size_t i = 0; i < nseg; i++) {
+    const size_t n = dst[i].count;
+    if (res[i].count != n || (has_src && src[i].count != n) || (has_cmp && cmp[i].count != n))
+      return -LFA_EINVAL;
+    if (!n) continue;
+    if ((has_src && !src[i].addr) || (has_cmp && !cmp[i].addr)) return -LFA_EINVAL;
+    if (!iov_written(range, dst[i].addr, n, esz) || !iov_written(range, res[i].addr, n, esz))
+      return -LFA_EINVAL;
+  }
+  return iov_disjoint(range);
+}
+
 int lfa_host_writev(enum lfa_op op, enum lfa_datatype dt, const struct lfa_ioc *dst,
                     const struct lfa_ioc *src, size_t nseg) {
   if (lfa_reduce_valid(dt, op)) return -LFA_EOPNOTSUPP;
@@ -297,6 +339,30 @@ int lfa_host_writev(enum lfa_op op, enum lfa_datatype dt, const struct lfa_ioc *
   int rc = lfa__iov_check(dst, src, 1, nseg, lfa_reduce_datatype_size(dt));
   for (size_t i = 0; i < nseg && !rc; i++)
     rc = lfa_host_write(op, dt, dst[i].addr, src[i].addr, dst[i].count);
+  return rc;
+}
+
+int lfa_host_readwritev(enum lfa_op op, enum lfa_datatype dt, const struct lfa_ioc *dst,
+                        const struct lfa_ioc *src, const struct lfa_ioc *res, size_t nseg) {
+  if (lfa_atomic_valid(dt, op, LFA_FETCH_ATOMIC)) return -LFA_EOPNOTSUPP;
+  if (!nseg) return 0;
+  const bool has_src = op != LFA_ATOMIC_READ;
+  int rc = lfa__iov_fetch_check(dst, src, has_src, nullptr, 0, res, nseg, lfa_datatype_size(dt));
+  for (size_t i = 0; i < nseg && !rc; i++)
+    rc = lfa_host_readwrite(op, dt, dst[i].addr, has_src ? src[i].addr : nullptr, res[i].addr,
+                            dst[i].count);
+  return rc;
+}
+
+int lfa_host_swapv(enum lfa_op op, enum lfa_datatype dt, const struct lfa_ioc *dst,
+                   const struct lfa_ioc *src, const struct lfa_ioc *cmp,
+                   const struct lfa_ioc *res, size_t nseg) {
+  if (lfa_atomic_valid(dt, op, LFA_COMPARE_ATOMIC)) return -LFA_EOPNOTSUPP;
+  if (!nseg) return 0;
+  int rc = lfa__iov_fetch_check(dst, src, 1, cmp, 1, res, nseg, lfa_datatype_size(dt));
+  for (size_t i = 0; i < nseg && !rc; i++)
+    rc = lfa_host_swap(op, dt, dst[i].addr, src[i].addr, cmp[i].addr, res[i].addr,
+                       dst[i].count);
   return rc;
 }
 

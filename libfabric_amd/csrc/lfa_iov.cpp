@@ -1,5 +1,6 @@
 // lfa_iov.cpp — the host side of the list (fi_ioc) forms: one launch for
-// every segment of a call (lfa_atomic_writev_async, lfa_reduce_treev_async).
+// every segment of a call (lfa_atomic_writev_async, lfa_reduce_treev_async,
+// lfa_atomic_readwritev_async, lfa_atomic_swapv_async).
 // The table's layout: lfa_iov.h; its builder: lfa_iov_table.h.
 #include <hip/hip_runtime_api.h>
 #include <pthread.h>
@@ -9,6 +10,9 @@
 
 extern "C" int lfa__iov_check(const struct lfa_ioc *, const struct lfa_ioc *, int, size_t,
                               size_t);
+extern "C" int lfa__iov_fetch_check(const struct lfa_ioc *, const struct lfa_ioc *, int,
+                                    const struct lfa_ioc *, int, const struct lfa_ioc *, size_t,
+                                    size_t);
 
 namespace {
 
@@ -21,8 +25,9 @@ namespace {
 // only a caller with more than kIovSlots such calls in flight waits for the
 // oldest launch (hipEventSynchronize).  Slots start empty and grow to the
 // largest table they have carried (a power of two from 64 KiB; at most
-// 128 KiB for LFA_IOV_MAX binary segments, 1 MiB for LFA_IOV_MAX segments of
-// 15 inputs), so steady state allocates nothing.
+// 128 KiB for LFA_IOV_MAX binary segments, 256 KiB for LFA_IOV_MAX fetch or
+// compare segments, 1 MiB for LFA_IOV_MAX segments of 15 inputs), so steady
+// state allocates nothing.
 constexpr int kIovSlots = 8;
 struct IovSlot {
   uint64_t *host = nullptr, *dev = nullptr;
@@ -180,6 +185,72 @@ int lfa_reduce_treev_async(enum lfa_op op, enum lfa_datatype dt,
   return iov_launch(t, stream, [&](const lfa_iov_args *a, unsigned ntile) {
     return copy ? kOps[LFA_ATOMIC_WRITE]->writev(LFA_UINT8, a, ntile, stream)
                 : kOps[op]->treev(dt, a, nsrc, ntile, stream);
+  });
+}
+
+int lfa_atomic_readwritev_async(enum lfa_op op, enum lfa_datatype dt,
+                                const struct lfa_ioc *dst, const struct lfa_ioc *src,
+                                const struct lfa_ioc *res, size_t nseg, void *stream) {
+  if ((unsigned)op >= LFA_READWRITE_OP_CNT || (unsigned)dt >= LFA_DATATYPE_CNT ||
+      !in_rw_table(op, dt))
+    return -LFA_EOPNOTSUPP;
+  if (!nseg) return 0;
+  const size_t esz = lfa_datatype_size(dt);
+  const bool has_src = op != LFA_ATOMIC_READ;
+  int rc = lfa__iov_fetch_check(dst, src, has_src, nullptr, 0, res, nseg, esz);
+  if (rc) return rc;
+  IovTable &t = t_iov;
+  t.reset(LFA_IOV_RW_NIN);
+  size_t only = 0;
+  for (size_t i = 0; i < nseg; i++) {
+    if (!dst[i].count) continue;
+    // ATOMIC_READ has no src: dst stands in its word, as launch_readwrite
+    // measures the path over (dst, res, dst)
+    const void *in[LFA_IOV_RW_NIN];
+    in[LFA_IOV_RW_SRC - LFA_IOV_IN] = has_src ? src[i].addr : dst[i].addr;
+    in[LFA_IOV_RW_RES - LFA_IOV_IN] = res[i].addr;
+    if ((rc = t.add(dst[i].addr, dst[i].count, in, esz))) return rc;
+    only = i;
+  }
+  if (!t.nseg()) return 0;
+  // One segment is what lfa_atomic_readwrite_async takes: its launcher chooses
+  // the tapered and nt-drained bodies by size, which a 256 MiB segment keeps.
+  if (t.nseg() == 1)
+    return kOps[op]->readwrite(dt, dst[only].addr, has_src ? src[only].addr : nullptr,
+                               res[only].addr, dst[only].count, stream);
+  return iov_launch(t, stream, [&](const lfa_iov_args *a, unsigned ntile) {
+    return kOps[op]->readwritev(dt, a, ntile, stream);
+  });
+}
+
+int lfa_atomic_swapv_async(enum lfa_op op, enum lfa_datatype dt, const struct lfa_ioc *dst,
+                           const struct lfa_ioc *src, const struct lfa_ioc *cmp,
+                           const struct lfa_ioc *res, size_t nseg, void *stream) {
+  if (op < LFA_CSWAP || op > LFA_MSWAP || (unsigned)dt >= LFA_DATATYPE_CNT ||
+      !in_swap_table(op, dt))
+    return -LFA_EOPNOTSUPP;
+  if (!nseg) return 0;
+  const size_t esz = lfa_datatype_size(dt);
+  int rc = lfa__iov_fetch_check(dst, src, 1, cmp, 1, res, nseg, esz);
+  if (rc) return rc;
+  IovTable &t = t_iov;
+  t.reset(LFA_IOV_SWAP_NIN);
+  size_t only = 0;
+  for (size_t i = 0; i < nseg; i++) {
+    if (!dst[i].count) continue;
+    const void *in[LFA_IOV_SWAP_NIN];
+    in[LFA_IOV_SWAP_SRC - LFA_IOV_IN] = src[i].addr;
+    in[LFA_IOV_SWAP_CMP - LFA_IOV_IN] = cmp[i].addr;
+    in[LFA_IOV_SWAP_RES - LFA_IOV_IN] = res[i].addr;
+    if ((rc = t.add(dst[i].addr, dst[i].count, in, esz))) return rc;
+    only = i;
+  }
+  if (!t.nseg()) return 0;
+  if (t.nseg() == 1)
+    return kOps[op]->swap(dt, dst[only].addr, src[only].addr, cmp[only].addr, res[only].addr,
+                          dst[only].count, stream);
+  return iov_launch(t, stream, [&](const lfa_iov_args *a, unsigned ntile) {
+    return kOps[op]->swapv(dt, a, ntile, stream);
   });
 }
 

@@ -12,7 +12,12 @@
  *                           grid), P = (nseg + 2) / 2
  *   words [P + s·R, …)      segment s: dst, count (elements), in[0 .. nin)
  *                           R = 2 + nin; nin = 1 for writev (src), nsrc for
- *                           treev
+ *                           treev, 2 for readwritev (src, res), 3 for swapv
+ *                           (src, cmp, res)
+ *
+ * The fetch and compare forms write `res` too; it is a pointer of the record
+ * like the inputs (the last one), and the kernels reach every word of a
+ * record through the LFA_IOV_* indices below.
  *
  * A table of at most LFA_IOV_INLINE words travels in the kernel arguments
  * (`inl`, tab == NULL); a larger one is copied to a device ring slot that
@@ -38,6 +43,19 @@ struct lfa_iov_args {
   uint32_t pad;
   uint64_t inl[LFA_IOV_INLINE];
 };
+
+/* Words of a record, from its first: dst, count, then the further pointers. */
+#define LFA_IOV_DST 0
+#define LFA_IOV_COUNT 1
+#define LFA_IOV_IN 2 /* in[k] is word LFA_IOV_IN + k */
+/* the further pointers of the fetch (nin = 2) and compare (nin = 3) records */
+#define LFA_IOV_RW_NIN 2
+#define LFA_IOV_RW_SRC (LFA_IOV_IN + 0)
+#define LFA_IOV_RW_RES (LFA_IOV_IN + 1)
+#define LFA_IOV_SWAP_NIN 3
+#define LFA_IOV_SWAP_SRC (LFA_IOV_IN + 0)
+#define LFA_IOV_SWAP_CMP (LFA_IOV_IN + 1)
+#define LFA_IOV_SWAP_RES (LFA_IOV_IN + 2)
 
 #define LFA_IOV_FN LFA_SPLIT_FN
 

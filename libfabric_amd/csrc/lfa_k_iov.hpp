@@ -1,5 +1,6 @@
 // lfa_k_iov.hpp — the list (fi_ioc) forms: every segment of a call combined
-// in ONE launch (lfa_atomic_writev_async, lfa_reduce_treev_async).
+// in ONE launch (lfa_atomic_writev_async, lfa_reduce_treev_async,
+// lfa_atomic_readwritev_async, lfa_atomic_swapv_async).
 // Part of lfa_kernels.hpp; included by it after the launchers.  Not included
 // on its own.  Table layout and tiling: lfa_iov.h.
 //
@@ -18,7 +19,9 @@
 //   element  aligned to the element, not co-aligned: one element per lane
 //   bytes    some operand not aligned to the element: byte-wise moves
 // so a call's result is bit for bit that of one lfa_atomic_write_async /
-// lfa_reduce_tree_async per segment.
+// lfa_reduce_tree_async / lfa_atomic_readwrite_async / lfa_atomic_swap_async
+// per segment.  The fetch and compare forms (fetch_iov) run the fetch
+// family's LDS-DMA tile, fetch_tile, on the vector path.
 #pragma once
 
 #include "lfa_iov.h"
@@ -68,7 +71,7 @@ __device__ __forceinline__ uint32_t iov_find(const IovArgs &a, uint32_t &tile) {
   }
   seg = __builtin_amdgcn_readfirstlane(seg);
   tile = __builtin_amdgcn_readfirstlane(tile);
-  return (uint32_t)lfa_iov_prefix_words(a.nseg) + seg * (2 + a.nin);
+  return (uint32_t)lfa_iov_prefix_words(a.nseg) + seg * (LFA_IOV_IN + a.nin);
 }
 
 // ---------------------------------------------------------------------------
@@ -80,9 +83,9 @@ __global__ __launch_bounds__(kLdsWaves * 64) void combine_iov(IovArgs a) {
   constexpr size_t E = sizeof(T), TE = LFA_IOV_TILE / E;
   uint32_t tile;
   const uint32_t r = iov_find(a, tile);
-  char *dst = (char *)iov_word(a, r);
-  const size_t cnt = iov_word(a, r + 1);
-  const char *src = (const char *)iov_word(a, r + 2);
+  char *dst = (char *)iov_word(a, r + LFA_IOV_DST);
+  const size_t cnt = iov_word(a, r + LFA_IOV_COUNT);
+  const char *src = (const char *)iov_word(a, r + LFA_IOV_IN);
   const uintptr_t pd = (uintptr_t)dst, ps = (uintptr_t)src;
   const unsigned t = threadIdx.x;
   if (pd % E || ps % E) {
@@ -127,9 +130,9 @@ __global__ __launch_bounds__(kBlock) void reduce_iov(IovTreeArgs ta) {
   const IovArgs &a = ta.a;
   uint32_t tile;
   const uint32_t r = iov_find(a, tile);
-  char *dst = (char *)iov_word(a, r);
-  const size_t cnt = iov_word(a, r + 1);
-  auto in = [&](int k) { return (const char *)iov_word(a, r + 2 + k); };
+  char *dst = (char *)iov_word(a, r + LFA_IOV_DST);
+  const size_t cnt = iov_word(a, r + LFA_IOV_COUNT);
+  auto in = [&](int k) { return (const char *)iov_word(a, r + LFA_IOV_IN + k); };
   const uintptr_t pd = (uintptr_t)dst;
   uintptr_t any = pd, mis = 0;
   for (uint32_t k = 0; k < a.nin; k++) {  // wave-uniform
@@ -172,9 +175,116 @@ __global__ __launch_bounds__(kBlock) void reduce_iov(IovTreeArgs ta) {
 }
 
 // ---------------------------------------------------------------------------
+// res[s][i] = dst[s][i], then dst[s][i] is updated: the fetch (readwritev) and
+// compare (swapv) tables, every segment s in one launch
+// ---------------------------------------------------------------------------
+// A segment's functor (lfa_k_fetch.hpp) from its record; the vector pointers
+// start `hb` bytes in, after the head.  ATOMIC_READ's record carries dst in
+// the src word (lfa_iov.cpp), which RwF<OP_READ> never dereferences.
+template <int OP, typename T, bool A>
+__device__ __forceinline__ void iov_functor(RwF<OP, T, A> &f, const IovArgs &a, uint32_t r,
+                                            size_t hb) {
+  static_assert(RwF<OP, T, A>::kIn <= LFA_IOV_RW_NIN, "src and res travel in the record");
+  char *d = (char *)iov_word(a, r + LFA_IOV_DST);
+  const char *s = (const char *)iov_word(a, r + LFA_IOV_RW_SRC);
+  char *res = (char *)iov_word(a, r + LFA_IOV_RW_RES);
+  f = RwF<OP, T, A>{d, s, res, (u32x4 *)(d + hb), (const u32x4 *)(s + hb), (u32x4 *)(res + hb)};
+}
+
+template <int OP, typename T, bool A>
+__device__ __forceinline__ void iov_functor(SwapF<OP, T, A> &f, const IovArgs &a, uint32_t r,
+                                            size_t hb) {
+  static_assert(SwapF<OP, T, A>::kIn == LFA_IOV_SWAP_NIN, "src, cmp and res travel in the record");
+  char *d = (char *)iov_word(a, r + LFA_IOV_DST);
+  const char *s = (const char *)iov_word(a, r + LFA_IOV_SWAP_SRC);
+  const char *c = (const char *)iov_word(a, r + LFA_IOV_SWAP_CMP);
+  char *res = (char *)iov_word(a, r + LFA_IOV_SWAP_RES);
+  f = SwapF<OP, T, A>{d,
+                      s,
+                      c,
+                      res,
+                      (u32x4 *)(d + hb),
+                      (const u32x4 *)(s + hb),
+                      (const u32x4 *)(c + hb),
+                      (u32x4 *)(res + hb)};
+}
+
+// FA / FB: one functor family's element-aligned and byte-wise members (RwF or
+// SwapF of one (OP, T)).  The path is launch_fetch's, decided here per segment
+// over ALL of the record's pointers (dst, src, [cmp,] res); whole-vector tiles
+// run fetch_tile as the contiguous launcher does below kSc1Bytes (4 KiB per
+// input per wave, write-through stores, the two-input body drained); its
+// buffer resources are cut from the functor's pointers, so from the record.
+template <typename FA, typename FB, typename T>
+__global__ __launch_bounds__(kLdsWaves * 64) void fetch_iov(IovArgs a) {
+  __shared__ u32x4 lds[FA::kIn][kLdsWaves][kUnroll][64];
+  constexpr size_t E = sizeof(T), TE = LFA_IOV_TILE / E;
+  uint32_t tile;
+  const uint32_t r = iov_find(a, tile);
+  const uintptr_t pd = (uintptr_t)iov_word(a, r + LFA_IOV_DST);
+  const size_t cnt = iov_word(a, r + LFA_IOV_COUNT);
+  uintptr_t any = pd, mis = 0;
+  for (uint32_t k = 0; k < a.nin; k++) {  // wave-uniform
+    const uintptr_t p = (uintptr_t)iov_word(a, r + LFA_IOV_IN + k);
+    any |= p;
+    mis |= p ^ pd;
+  }
+  const unsigned t = threadIdx.x;
+  // Element work of this tile: [0, n0) and [off1, off1 + n1), one call site;
+  // `bytes`: some operand is not aligned to the element and all move byte-wise.
+  const bool bytes = any % E != 0;
+  const size_t head = bytes ? 0 : lfa_split_head(pd, cnt, E), n0 = tile == 0 ? head : 0;
+  FA fa;
+  FB fb;
+  iov_functor(fa, a, r, head * E);
+  iov_functor(fb, a, r, 0);
+  size_t off1, n1;
+  if (!bytes && mis % 16 == 0) {
+    const size_t nvec = (cnt - head) * E / 16;
+    const unsigned w = wave_id<true>(), l = t % 64;
+    fetch_tile<kUnroll, kUnroll, kStoreSc1, FA, FA::kIn == 2>(
+        fa, nvec, (size_t)tile * kIovTileVecs + (size_t)w * 64 * kUnroll, lds, w, l);
+    // the elements after the last whole vector: once, by the tile they lie in
+    off1 = head + nvec * (16 / E);
+    n1 = tile == nvec / kIovTileVecs ? cnt - off1 : 0;
+  } else {
+    const size_t rest = cnt - head, i0 = (size_t)tile * TE;
+    off1 = head + i0;
+    n1 = rest - i0 < TE ? rest - i0 : TE;
+  }
+  for (size_t i = t; i < n0 + n1; i += kLdsWaves * 64) {
+    const size_t k = i < n0 ? i : off1 + (i - n0);
+    if (E > 1 && bytes) fb.elem(k);
+    else fa.elem(k);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // launchers: the table is built and validated by lfa_iov.cpp
 // ---------------------------------------------------------------------------
 static_assert(kBlock == kLdsWaves * 64, "one workgroup shape for both forms");
+
+template <int OP, typename T>
+static int launch_readwritev(const IovArgs &a, unsigned ntile, hipStream_t s) {
+  if constexpr (!rw_supported<OP, T>()) {
+    return -LFA_EOPNOTSUPP;
+  } else {
+    hipLaunchKernelGGL((fetch_iov<RwF<OP, T, true>, RwF<OP, T, false>, T>), dim3(ntile),
+                       dim3(kBlock), 0, s, a);
+    return launch_rc();
+  }
+}
+
+template <int OP, typename T>
+static int launch_swapv(const IovArgs &a, unsigned ntile, hipStream_t s) {
+  if constexpr (!swap_supported<OP, T>()) {
+    return -LFA_EOPNOTSUPP;
+  } else {
+    hipLaunchKernelGGL((fetch_iov<SwapF<OP, T, true>, SwapF<OP, T, false>, T>), dim3(ntile),
+                       dim3(kBlock), 0, s, a);
+    return launch_rc();
+  }
+}
 
 template <int OP, typename T>
 static int launch_writev(const IovArgs &a, unsigned ntile, hipStream_t s) {

@@ -19,6 +19,8 @@ struct lfa_oneshot;  /* lfa_signal.h */
 typedef int (*lfa_launch_write_t)(int dt, void *dst, const void *src, size_t cnt, void *stream);
 typedef int (*lfa_launch_writev_t)(int dt, const struct lfa_iov_args *a, unsigned ntile,
                                    void *stream);
+/* the fetch and compare list forms: the record says which pointer is which (lfa_iov.h) */
+typedef lfa_launch_writev_t lfa_launch_fetchv_t;
 typedef int (*lfa_launch_tree_t)(int dt, void *dst, const void *const *srcs, int nsrc,
                                  size_t cnt, void *stream);
 typedef int (*lfa_launch_treev_t)(int dt, const struct lfa_iov_args *a, int nsrc,
@@ -40,6 +42,8 @@ struct lfa_op_launch {
   lfa_launch_oneshot_t oneshot;     /* ops 0..9 */
   lfa_launch_readwrite_t readwrite; /* ops 0..11 */
   lfa_launch_swap_t swap;           /* ops 12..18 */
+  lfa_launch_fetchv_t readwritev;   /* ops 0..11 */
+  lfa_launch_fetchv_t swapv;        /* ops 12..18 */
 };
 
 #endif /* LFA_LAUNCH_H */
