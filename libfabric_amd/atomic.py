@@ -17,6 +17,9 @@ Mirrors the reference's L4 combine interface (include/ofi_atomic.h:45-90):
                                     fi_compare_atomicv)
   host_readwrite / host_swap        the fetch and compare tables on host
                                     buffers (lfa_host_readwrite / lfa_host_swap)
+  write_as / reduce_tree_as         test-only: write / reduce_tree with the
+                                    vector body's form chosen as if the body
+                                    were `as_bytes` bytes
   reduce_valid / reduce_datatype_size  what write / reduce_tree / the
                                     collectives take: the table's columns plus
                                     DT.FLOAT16 and DT.BFLOAT16
@@ -178,6 +181,41 @@ def reduce_tree_put(op: int, dt: int, dsts: list[torch.Tensor], srcs: list[torch
                                          cnt, _stream_handle(stream))
     if rc:
         raise LfaError(rc, f"lfa_reduce_tree_put_async({OP(op).name},{DT(dt).name})")
+
+
+# ------------------------------------------------- forced forms (tests) ----
+# write / reduce_tree with the vector body's form chosen as if the body were
+# `as_bytes` bytes (lfa_split.h: lfa_form_write / lfa_form_tree); everything
+# else about the launch follows the real size.  For
+# tests/test_sweep_forms_gpu.py, which runs the forms a launcher only takes
+# from 32 or 192 MiB on small buffers; no product caller.
+
+def write_as(op: int, dt: int, dst: torch.Tensor, src: torch.Tensor, cnt: int,
+             as_bytes: int, stream=None) -> None:
+    _check_dev(dst, "dst")
+    _check_dev(src, "src")
+    esz = reduce_datatype_size(dt)
+    if cnt * esz > dst.nbytes or cnt * esz > src.nbytes:
+        raise ValueError("cnt exceeds buffer size")
+    rc = lib().lfa__write_as(int(op), int(dt), dst.data_ptr(), src.data_ptr(), cnt,
+                             _stream_handle(stream), as_bytes)
+    if rc:
+        raise LfaError(rc, f"lfa__write_as({op},{dt},{as_bytes})")
+
+
+def reduce_tree_as(op: int, dt: int, dst: torch.Tensor, srcs: list[torch.Tensor], cnt: int,
+                   as_bytes: int, stream=None) -> None:
+    _check_dev(dst, "dst")
+    for i, s in enumerate(srcs):
+        _check_dev(s, f"srcs[{i}]")
+    esz = reduce_datatype_size(dt)
+    if any(cnt * esz > s.nbytes for s in srcs) or cnt * esz > dst.nbytes:
+        raise ValueError("cnt exceeds buffer size")
+    arr = (ctypes.c_void_p * len(srcs))(*[s.data_ptr() for s in srcs])
+    rc = lib().lfa__tree_as(int(op), int(dt), dst.data_ptr(), arr, len(srcs), cnt,
+                            _stream_handle(stream), as_bytes)
+    if rc:
+        raise LfaError(rc, f"lfa__tree_as({op},{dt},{as_bytes})")
 
 
 # ------------------------------------------------------------- list forms --

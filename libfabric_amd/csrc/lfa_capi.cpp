@@ -109,7 +109,7 @@ void sync_entry(void *dst, const void *src, size_t cnt) {
     note_error(rc);
     return;
   }
-  sync_finish("combine", OP, DT, kOps[OP]->write(DT, dst, src, cnt, nullptr));
+  sync_finish("combine", OP, DT, kOps[OP]->write(DT, dst, src, cnt, nullptr, 0));
 }
 
 // A table's cell: the entry where the reference's table has one, else NULL.
@@ -164,12 +164,30 @@ int lfa_atomic_last_error(void) {
   return rc;
 }
 
-int lfa_atomic_write_async(enum lfa_op op, enum lfa_datatype dt, void *dst,
-                           const void *src, size_t cnt, void *stream) {
+// The write and tree launches share their validation with the lfa__write_as
+// and lfa__tree_as entries below, which differ only in passing as_bytes on.
+static int write_as(enum lfa_op op, enum lfa_datatype dt, void *dst, const void *src,
+                    size_t cnt, void *stream, size_t as_bytes) {
   if ((unsigned)op >= LFA_WRITE_OP_CNT || !reducible(op, dt))
     return -LFA_EOPNOTSUPP;
   if (cnt && (!dst || !src)) return -LFA_EINVAL;
-  return kOps[op]->write(dt, dst, src, cnt, stream);
+  return kOps[op]->write(dt, dst, src, cnt, stream, as_bytes);
+}
+
+static int tree_check(enum lfa_op op, enum lfa_datatype dt, void *dst,
+                      const void *const *srcs, int nsrc, size_t cnt) {
+  if ((unsigned)op > LFA_BXOR || !reducible(op, dt))
+    return -LFA_EOPNOTSUPP;
+  if (nsrc < 1 || nsrc > LFA_TREE_MAX || !srcs || (cnt && !dst))
+    return -LFA_EINVAL;
+  for (int k = 0; k < nsrc; k++)
+    if (cnt && !srcs[k]) return -LFA_EINVAL;
+  return 0;
+}
+
+int lfa_atomic_write_async(enum lfa_op op, enum lfa_datatype dt, void *dst,
+                           const void *src, size_t cnt, void *stream) {
+  return write_as(op, dt, dst, src, cnt, stream, 0);
 }
 
 int lfa_atomic_readwrite_async(enum lfa_op op, enum lfa_datatype dt, void *dst,
@@ -196,12 +214,7 @@ int lfa_atomic_swap_async(enum lfa_op op, enum lfa_datatype dt, void *dst,
 int lfa_reduce_tree_async(enum lfa_op op, enum lfa_datatype dt, void *dst,
                           const void *const *srcs, int nsrc, size_t cnt,
                           void *stream) {
-  if ((unsigned)op > LFA_BXOR || !reducible(op, dt))
-    return -LFA_EOPNOTSUPP;
-  if (nsrc < 1 || nsrc > LFA_TREE_MAX || !srcs || (cnt && !dst))
-    return -LFA_EINVAL;
-  for (int k = 0; k < nsrc; k++)
-    if (cnt && !srcs[k]) return -LFA_EINVAL;
+  if (int rc = tree_check(op, dt, dst, srcs, nsrc, cnt)) return rc;
   // One input is a copy (a one-member group's allreduce): from 16 MiB the
   // write table's ATOMIC_WRITE body beats hipMemcpyAsync D2D (83.3 vs 98.8 us
   // at 256 MiB, profiles/r02_probe_copy.log); below, the tree launcher's
@@ -210,7 +223,24 @@ int lfa_reduce_tree_async(enum lfa_op op, enum lfa_datatype dt, void *dst,
   if (nsrc == 1 && dst != srcs[0] && bytes >= ((size_t)16 << 20))
     return lfa_atomic_write_async(LFA_ATOMIC_WRITE, LFA_UINT8, dst, srcs[0], bytes,
                                   stream);
-  return kOps[op]->tree(dt, dst, srcs, nsrc, cnt, stream);
+  return kOps[op]->tree(dt, dst, srcs, nsrc, cnt, stream, 0);
+}
+
+// Test-only entries (internal, as lfa__tune_* in liblfa_tune.so; not in
+// include/lfa_atomic.h): the write and tree calls above with the vector
+// body's form chosen as if the body were `as_bytes` bytes (lfa_split.h; 0: by
+// the real size), so that tests/test_sweep_forms_gpu.py runs every form those
+// launchers only take from 32 or 192 MiB on a 40 KiB buffer.  The tree entry
+// goes to the tree launcher whatever nsrc is.
+int lfa__write_as(int op, int dt, void *dst, const void *src, size_t cnt, void *stream,
+                  size_t as_bytes) {
+  return write_as((lfa_op)op, (lfa_datatype)dt, dst, src, cnt, stream, as_bytes);
+}
+
+int lfa__tree_as(int op, int dt, void *dst, const void *const *srcs, int nsrc, size_t cnt,
+                 void *stream, size_t as_bytes) {
+  if (int rc = tree_check((lfa_op)op, (lfa_datatype)dt, dst, srcs, nsrc, cnt)) return rc;
+  return kOps[op]->tree(dt, dst, srcs, nsrc, cnt, stream, as_bytes);
 }
 
 int lfa_reduce_tree_put_async(enum lfa_op op, enum lfa_datatype dt,

@@ -154,12 +154,13 @@ static int by_iov_fetch_type(int dt, F &&f) {
 // Which forms op LFA_OP has: each is a function where it does, and a null
 // pointer of the member's type where it does not.
 #if LFA_OP <= 11 && LFA_OP != 10
-static int op_write(int dt, void *dst, const void *src, size_t cnt, void *stream) {
+static int op_write(int dt, void *dst, const void *src, size_t cnt, void *stream,
+                    size_t as_bytes) {
   // dt | LFA_WRITE_MAPPED: operands on their host mappings (lfa_stage.cpp)
   const bool mapped = (dt & LFA_WRITE_MAPPED) != 0;
   return lfa::by_reduce_type<LFA_OP>(dt & ~LFA_WRITE_MAPPED, [&](auto *tag) {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
-    return lfa::launch_write<LFA_OP, T>(dst, src, cnt, (hipStream_t)stream, mapped);
+    return lfa::launch_write<LFA_OP, T>(dst, src, cnt, (hipStream_t)stream, mapped, as_bytes);
   });
 }
 
@@ -184,11 +185,11 @@ static int op_treev(int dt, const lfa_iov_args *a, int nsrc, unsigned ntile,
 }
 
 static int op_tree(int dt, void *dst, const void *const *srcs, int nsrc, size_t cnt,
-                   void *stream) {
+                   void *stream, size_t as_bytes) {
   return lfa::by_reduce_type<LFA_OP>(dt, [&](auto *tag) {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
-    return lfa::launch_tree<LFA_OP, T>(dst, srcs, nsrc, cnt,
-                                       (hipStream_t)stream);
+    return lfa::launch_tree<LFA_OP, T>(dst, srcs, nsrc, cnt, (hipStream_t)stream, -1,
+                                       as_bytes);
   });
 }
 

@@ -136,7 +136,7 @@ int lfa_atomic_writev_async(enum lfa_op op, enum lfa_datatype dt,
   // their tiling and store policy by size (taper, nt stores from 192 MiB),
   // which a 256 MiB segment keeps.
   if (t.nseg() == 1)
-    return kOps[op]->write(dt, dst[only].addr, src[only].addr, dst[only].count, stream);
+    return kOps[op]->write(dt, dst[only].addr, src[only].addr, dst[only].count, stream, 0);
   return iov_launch(t, stream, [&](const lfa_iov_args *a, unsigned ntile) {
     return kOps[op]->writev(dt, a, ntile, stream);
   });

@@ -12,9 +12,16 @@ namespace lfa {
 // bench.py --tune; see DESIGN.md "Kernel tuning"): LDS-DMA staging, 4 KiB of
 // each operand per wave, nt loads and stores.
 constexpr int kUnroll = 4;
-// combine_lds_taper from this many bytes per operand (up to kSc1Bytes; the
+
+// Which form of the body launch_write and launch_tree_body take by its size
+// is lfa_split.h's lfa_form_write / lfa_form_tree (thresholds there): plain C,
+// checked on the host by tools/split_host_check.cpp.  Those two launchers'
+// last argument, as_bytes, is theirs: 0 in the product, a pretended body size
+// from the lfa__write_as and lfa__tree_as test entries (lfa_capi.cpp).
+// launch_fetch decides inline.
+
+// combine_lds_taper from LFA_TAPER_BYTES per operand (up to kSc1Bytes; the
 // nt-store path above keeps the uniform grid), the last 1/kTaperDiv tapered
-constexpr size_t kTaperBytes = (size_t)32 << 20;
 constexpr size_t kTaperDiv = 8;
 
 static inline unsigned grid_for(size_t work, size_t per_block, unsigned cap) {
@@ -33,7 +40,7 @@ static inline int launch_rc() { return hipGetLastError() == hipSuccess ? 0 : -LF
 // the tail — or, off the vector path, the whole buffer (sp.head == cnt).
 template <int OP, typename T>
 static int launch_write(void *dst, const void *src, size_t cnt,
-                        hipStream_t s, bool mapped = false) {
+                        hipStream_t s, bool mapped = false, size_t as_bytes = 0) {
   if constexpr (!supported<OP, T>()) {
     return -LFA_EOPNOTSUPP;
   } else {
@@ -53,25 +60,28 @@ static int launch_write(void *dst, const void *src, size_t cnt,
       const u32x4 *v = (const u32x4 *)((const char *)src + sp.head * E);
       constexpr size_t hv = (size_t)kLdsWaves * 64 * kUnroll;
       const dim3 grid(grid_for(nvec, hv, 0x7fffffffu));
-      if (mapped) {
-        // host-mapped operands (lfa_atomic_write_staged's zero-copy form):
-        // PCIe-bound, so the tiling does not matter; the plain write-through
-        // body at every size keeps these ~10 ms launches out of the device
-        // kernels' instantiations in traces (rocprofv3 stats per kernel)
-        hipLaunchKernelGGL((combine_lds<OP, T, kUnroll, kStoreSc1>), grid,
-                           dim3(kLdsWaves * 64), 0, s, d, v, nvec);
-      } else if (nvec * 16 >= kTaperBytes && nvec * 16 < kSc1Bytes) {
-        // the last 1/kTaperDiv of the vectors in 1-KiB tiles
-        const lfa_taper tp = lfa_split_taper(nvec, kTaperDiv, hv, kLdsWaves * 64);
-        hipLaunchKernelGGL((combine_lds_taper<OP, T, kUnroll, kStoreSc1>),
-                           dim3(tp.nhead + tp.ntail), dim3(kLdsWaves * 64), 0, s, d, v, nvec,
-                           tp.split, tp.nhead);
-      } else if (nvec * 16 < kSc1Bytes)
-        hipLaunchKernelGGL((combine_lds<OP, T, kUnroll, kStoreSc1>), grid,
-                           dim3(kLdsWaves * 64), 0, s, d, v, nvec);
-      else
-        hipLaunchKernelGGL((combine_lds<OP, T, kUnroll, kStoreNt>), grid,
-                           dim3(kLdsWaves * 64), 0, s, d, v, nvec);
+      // host-mapped operands (lfa_atomic_write_staged's zero-copy form) are
+      // PCIe-bound, so the tiling does not matter; the plain write-through
+      // body at every size keeps these ~10 ms launches out of the device
+      // kernels' instantiations in traces (rocprofv3 stats per kernel)
+      switch (lfa_form_write(lfa_form_bytes(nvec, as_bytes), mapped)) {
+        case LFA_WRITE_TAPER: {
+          // the last 1/kTaperDiv of the vectors in 1-KiB tiles
+          const lfa_taper tp = lfa_split_taper(nvec, kTaperDiv, hv, kLdsWaves * 64);
+          hipLaunchKernelGGL((combine_lds_taper<OP, T, kUnroll, kStoreSc1>),
+                             dim3(tp.nhead + tp.ntail), dim3(kLdsWaves * 64), 0, s, d, v, nvec,
+                             tp.split, tp.nhead);
+          break;
+        }
+        case LFA_WRITE_SC1:
+          hipLaunchKernelGGL((combine_lds<OP, T, kUnroll, kStoreSc1>), grid,
+                             dim3(kLdsWaves * 64), 0, s, d, v, nvec);
+          break;
+        case LFA_WRITE_NT:
+          hipLaunchKernelGGL((combine_lds<OP, T, kUnroll, kStoreNt>), grid,
+                             dim3(kLdsWaves * 64), 0, s, d, v, nvec);
+          break;
+      }
     }
     if (sp.head + sp.tail)
       hipLaunchKernelGGL((combine_elem<OP, T>),
@@ -97,8 +107,9 @@ constexpr unsigned kTreeCapLds = 41u << 10;
 
 template <int OP, typename T, int NLEAF>
 static void launch_tree_body(const TreeArgs &b, int nsrc, u32x4 *dst,
-                             size_t nvec, hipStream_t s, int variant = -1) {
-  // Product choice (bench.py --tune-tree, profiles/r01_tune_tree_sc1.log):
+                             size_t nvec, hipStream_t s, int variant = -1,
+                             size_t as_bytes = 0) {
+  // Product choice, lfa_form_tree (bench.py --tune-tree, profiles/r01_tune_tree_sc1.log):
   // below kSc1Bytes of output the U=2 chunk form with write-through stores
   // wins at every fan-in (2..16 inputs: 58.9/53.4/52.1/51.7 us against
   // 63.2/58.2/53.9/51.7 for the nt-store forms, 256 MiB of inputs).
@@ -110,8 +121,7 @@ static void launch_tree_body(const TreeArgs &b, int nsrc, u32x4 *dst,
   // 4 inputs 55.44 -> 53.10 and 55.00 -> 53.52 us, 8 inputs 53.98 -> 52.84 and
   // 53.84 -> 52.92 us; 2 inputs lose (58.8 -> 61.8) and 16 tie, so they keep
   // the full occupancy.
-  const unsigned cap_lds =
-      (variant < 0 && nvec * 16 < kSc1Bytes && nsrc >= 3 && nsrc <= 8) ? kTreeCapLds : 0u;
+  //
   // Round 5: at 8-15 inputs of >= 4-byte lanes the P2P push kernel's body
   // with one output (4 KiB per wave per input through tile-sized buffer
   // descriptors, nt loads, write-through stores) beat that form: 8 inputs
@@ -119,9 +129,16 @@ static void launch_tree_body(const TreeArgs &b, int nsrc, u32x4 *dst,
   // lost (52.74 -> 53.22), at 2 tied (bench.py --tune-tree variants -1 / 25,
   // profiles/r05_tune_tree_putbody.json)
   constexpr bool kPutBody = NLEAF == 8 && sizeof(T) >= 4;
-  if (variant < 0 && nvec * 16 < kSc1Bytes && kPutBody) variant = 25;
-  if (variant < 0 && nvec * 16 < kSc1Bytes) variant = 11;
-  if (variant < 0) variant = nsrc <= 2 ? 3 : nsrc > 8 ? 2 : 1;
+  // From kSc1Bytes of output: the LDS-DMA form at 2 inputs, the chunk forms
+  // with nt stores above (U = 2 past 8 inputs).  An explicit variant (the
+  // tuning library) is taken as it is, without the LDS cap.
+  unsigned cap_lds = 0;
+  if (variant < 0) {
+    const lfa_tree_form f =
+        lfa_form_tree(lfa_form_bytes(nvec, as_bytes), nsrc, NLEAF, sizeof(T));
+    variant = f.variant;
+    if (f.cap_lds) cap_lds = kTreeCapLds;
+  }
   // nsrc lies in [NLEAF, 2·NLEAF): only these forms are reachable from the
   // product choice, so only they are instantiated into liblfa.so (the
   // tuning library times every form at every fan-in: launch_tree_tune_form,
@@ -197,21 +214,21 @@ static int tree_leaves(TreeArgs &a, const void *const *srcs, int nsrc) {
 struct ProductTreeBody {
   template <int OP, typename T, int NLEAF>
   static void launch(const TreeArgs &b, int nsrc, u32x4 *dst, size_t nvec,
-                     hipStream_t s, int variant) {
-    launch_tree_body<OP, T, NLEAF>(b, nsrc, dst, nvec, s, variant);
+                     hipStream_t s, int variant, size_t as_bytes) {
+    launch_tree_body<OP, T, NLEAF>(b, nsrc, dst, nvec, s, variant, as_bytes);
   }
 };
 
 template <int OP, typename T, int NLEAF, typename Body = ProductTreeBody>
 static int launch_tree_n(const TreeArgs &a, int nsrc, void *dst, const lfa_split &sp,
-                         hipStream_t s, int variant) {
+                         hipStream_t s, int variant, size_t as_bytes) {
   constexpr size_t E = sizeof(T);
   if (sp.nvec) {
     TreeArgs b = a;
     for (int k = 0; k < kMaxLeaf; k++)
       if (b.in[k]) b.in[k] = (const char *)b.in[k] + sp.head * E;
     Body::template launch<OP, T, NLEAF>(b, nsrc, (u32x4 *)((char *)dst + sp.head * E),
-                                        sp.nvec, s, variant);
+                                        sp.nvec, s, variant, as_bytes);
   }
   if (sp.head + sp.tail)
     hipLaunchKernelGGL((reduce_tree_elem<OP, T, NLEAF>),
@@ -222,7 +239,7 @@ static int launch_tree_n(const TreeArgs &a, int nsrc, void *dst, const lfa_split
 
 template <int OP, typename T, typename Body = ProductTreeBody>
 static int launch_tree(void *dst, const void *const *srcs, int nsrc,
-                       size_t cnt, hipStream_t s, int variant = -1) {
+                       size_t cnt, hipStream_t s, int variant = -1, size_t as_bytes = 0) {
   if constexpr (!supported<OP, T>()) {
     return -LFA_EOPNOTSUPP;
   } else {
@@ -249,11 +266,11 @@ static int launch_tree(void *dst, const void *const *srcs, int nsrc,
     if ((uintptr_t)dst % 16) path = LFA_PATH_ELEM;
     const lfa_split sp = lfa_split_of(path, (uintptr_t)dst, cnt, E);
     switch (pof2) {
-      case 2: return launch_tree_n<OP, T, 2, Body>(a, nsrc, dst, sp, s, variant);
-      case 4: return launch_tree_n<OP, T, 4, Body>(a, nsrc, dst, sp, s, variant);
-      case 8: return launch_tree_n<OP, T, 8, Body>(a, nsrc, dst, sp, s, variant);
-      case 16: return launch_tree_n<OP, T, 16, Body>(a, nsrc, dst, sp, s, variant);
-      case 32: return launch_tree_n<OP, T, 32, Body>(a, nsrc, dst, sp, s, variant);
+      case 2: return launch_tree_n<OP, T, 2, Body>(a, nsrc, dst, sp, s, variant, as_bytes);
+      case 4: return launch_tree_n<OP, T, 4, Body>(a, nsrc, dst, sp, s, variant, as_bytes);
+      case 8: return launch_tree_n<OP, T, 8, Body>(a, nsrc, dst, sp, s, variant, as_bytes);
+      case 16: return launch_tree_n<OP, T, 16, Body>(a, nsrc, dst, sp, s, variant, as_bytes);
+      case 32: return launch_tree_n<OP, T, 32, Body>(a, nsrc, dst, sp, s, variant, as_bytes);
       default: return -LFA_EINVAL;
     }
   }

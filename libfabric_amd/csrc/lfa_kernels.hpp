@@ -136,7 +136,7 @@ constexpr int kLdsWaves = 4;
 // 256 MiB (rocprofv3 kernel durations, profiles/r01_rocprof_store_policy.csv),
 // so launches below kSc1Bytes write through.
 constexpr int kStoreNt = 2, kStoreSc1 = 16;
-constexpr size_t kSc1Bytes = (size_t)192 << 20;
+constexpr size_t kSc1Bytes = LFA_SC1_BYTES;  // lfa_split.h, with the form choosers
 
 // s_waitcnt vmcnt(N) alone (expcnt / lgkmcnt fields at their no-wait
 // maximum): every vector-memory operation of this wave but the N youngest

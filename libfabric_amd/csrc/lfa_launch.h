@@ -6,7 +6,10 @@
  * entries; a form the op does not have is NULL.  Both sides take the
  * signatures from here.  Every entry returns 0 or a negative LFA_E* code;
  * `dt` is an enum lfa_datatype (write: | LFA_WRITE_MAPPED, lfa_signal.h),
- * `stream` a hipStream_t.
+ * `stream` a hipStream_t.  write and tree end in `as_bytes`: 0 from every
+ * product caller; otherwise the vector body's form is chosen as if the body
+ * were that many bytes (lfa_split.h; the lfa__write_as / lfa__tree_as test
+ * entries).
  */
 #ifndef LFA_LAUNCH_H
 #define LFA_LAUNCH_H
@@ -16,13 +19,14 @@
 struct lfa_iov_args; /* lfa_iov.h */
 struct lfa_oneshot;  /* lfa_signal.h */
 
-typedef int (*lfa_launch_write_t)(int dt, void *dst, const void *src, size_t cnt, void *stream);
+typedef int (*lfa_launch_write_t)(int dt, void *dst, const void *src, size_t cnt, void *stream,
+                                  size_t as_bytes);
 typedef int (*lfa_launch_writev_t)(int dt, const struct lfa_iov_args *a, unsigned ntile,
                                    void *stream);
 /* the fetch and compare list forms: the record says which pointer is which (lfa_iov.h) */
 typedef lfa_launch_writev_t lfa_launch_fetchv_t;
 typedef int (*lfa_launch_tree_t)(int dt, void *dst, const void *const *srcs, int nsrc,
-                                 size_t cnt, void *stream);
+                                 size_t cnt, void *stream, size_t as_bytes);
 typedef int (*lfa_launch_treev_t)(int dt, const struct lfa_iov_args *a, int nsrc,
                                   unsigned ntile, void *stream);
 typedef int (*lfa_launch_treeput_t)(int dt, void *const *dsts, int ndst, const void *const *srcs,

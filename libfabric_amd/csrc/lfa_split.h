@@ -1,6 +1,7 @@
 /* lfa_split.h — how one buffer of a call is cut up, in one place: the path its
  * operands' addresses permit, the head / vector body / tail of the vector
- * path, and the tapered grid of a vector body.  Shared by every launcher
+ * path, the tapered grid of a vector body, and the form of that body a
+ * launcher picks by size (lfa_form_write, lfa_form_tree).  Shared by every launcher
  * (lfa_k_launch.hpp), the list kernels and their host side (lfa_iov.h) and
  * the tuning library.  Plain C: no HIP types.
  */
@@ -79,6 +80,69 @@ LFA_SPLIT_FN struct lfa_taper lfa_split_taper(size_t nvec, size_t div, size_t hv
   t.nhead = (unsigned)(t.split / hv);
   t.ntail = (unsigned)((nvec - t.split + tv - 1) / tv);
   return t;
+}
+
+/* Which form of a vector body launch_write and launch_tree_body run, by the body's size in bytes
+ * per operand (nvec * 16).  The launchers (lfa_k_launch.hpp) switch on these
+ * and on nothing else; the measurements behind every threshold are quoted
+ * there.  Pure functions of their arguments: tools/split_host_check.cpp
+ * prints them around every threshold. */
+#define LFA_TAPER_BYTES ((size_t)32 << 20)       /* write: tapered tail from here */
+#define LFA_SC1_BYTES ((size_t)192 << 20)        /* below: write-through stores; from here: nt */
+
+/* A launcher's `as_bytes` argument: 0 chooses by the real body, anything
+ * else as if the body were that many bytes.  Only the form follows it; the
+ * split, the grid and the kernel arguments come from the real size.  The
+ * product passes 0; the lfa__write_as / lfa__tree_as entries (lfa_capi.cpp)
+ * let the tests run every large-size form on a small buffer. */
+LFA_SPLIT_FN size_t lfa_form_bytes(size_t nvec, size_t as_bytes) {
+  return as_bytes ? as_bytes : nvec * 16;
+}
+
+enum lfa_write_form {
+  LFA_WRITE_SC1,   /* combine_lds, write-through stores */
+  LFA_WRITE_TAPER, /* combine_lds_taper, write-through stores */
+  LFA_WRITE_NT     /* combine_lds, nt stores, drained (combine_drain) */
+};
+
+/* mapped: host-mapped operands (lfa_atomic_write_staged's zero-copy form). */
+LFA_SPLIT_FN enum lfa_write_form lfa_form_write(size_t body_bytes, int mapped) {
+  if (mapped) return LFA_WRITE_SC1;
+  if (body_bytes >= LFA_SC1_BYTES) return LFA_WRITE_NT;
+  return body_bytes >= LFA_TAPER_BYTES ? LFA_WRITE_TAPER : LFA_WRITE_SC1;
+}
+
+/* The tree's vector body, under the numbers bench.py --tune-tree gives the
+ * forms: reduce_tree_chunk<.., 1> (1) and <.., 2> (2) with nt stores,
+ * reduce_tree_lds (3), reduce_tree_chunk<.., 2> with write-through stores
+ * (11), reduce_tree_put's body with one output (25). */
+enum {
+  LFA_TREE_CHUNK1 = 1,
+  LFA_TREE_CHUNK2 = 2,
+  LFA_TREE_LDS = 3,
+  LFA_TREE_CHUNK2_SC1 = 11,
+  LFA_TREE_PUT = 25
+};
+
+struct lfa_tree_form {
+  int variant;
+  int cap_lds; /* LFA_TREE_CHUNK2_SC1 only: launch with the 41 KiB of idle LDS */
+};
+
+/* nsrc in [nleaf, 2 * nleaf), nleaf a power of two, esz the element size. */
+LFA_SPLIT_FN struct lfa_tree_form lfa_form_tree(size_t body_bytes, int nsrc, int nleaf,
+                                                size_t esz) {
+  struct lfa_tree_form f;
+  f.cap_lds = 0;
+  if (body_bytes >= LFA_SC1_BYTES) {
+    f.variant = nsrc <= 2 ? LFA_TREE_LDS : nsrc > 8 ? LFA_TREE_CHUNK2 : LFA_TREE_CHUNK1;
+  } else if (nleaf == 8 && esz >= 4) {
+    f.variant = LFA_TREE_PUT;
+  } else {
+    f.variant = LFA_TREE_CHUNK2_SC1;
+    f.cap_lds = nsrc >= 3 && nsrc <= 8;
+  }
+  return f;
 }
 
 #endif /* LFA_SPLIT_H */

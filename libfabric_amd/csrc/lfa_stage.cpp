@@ -267,7 +267,7 @@ int lfa_atomic_write_staged(enum lfa_op op, enum lfa_datatype dt, void *dst,
     // buffers, no HBM round trip (256 MiB float SUM, both pinned: 9.96 ms
     // against 11.22 ms staged, profiles/r05_zero_copy.log)
     int ret = staging_acquire(c, 0);
-    if (!ret) ret = kOps[op]->write(dt | LFA_WRITE_MAPPED, zd, zs, cnt, c.s_out);
+    if (!ret) ret = kOps[op]->write(dt | LFA_WRITE_MAPPED, zd, zs, cnt, c.s_out, 0);
     if (hipStreamSynchronize(c.s_out) != hipSuccess && !ret) ret = -LFA_EIO;
     pthread_mutex_unlock(&c.lock);
     for (int i : reg) temp_drop(i);
@@ -286,7 +286,7 @@ int lfa_atomic_write_staged(enum lfa_op op, enum lfa_datatype dt, void *dst,
                      c.s_in);
       hipEventRecord(c.in_done[k], c.s_in);
       hipStreamWaitEvent(c.s_out, c.in_done[k], 0);
-      ret = kOps[op]->write(dt, dd, ds, n, c.s_out);
+      ret = kOps[op]->write(dt, dd, ds, n, c.s_out, 0);
       hipMemcpyAsync((char *)dst + off * esz, dd, n * esz, hipMemcpyDefault, c.s_out);
       hipEventRecord(c.out_done[k], c.s_out);
     }

@@ -420,7 +420,7 @@ namespace lfa {
 struct TuneTreeBody {
   template <int OP, typename T, int NLEAF>
   static void launch(const TreeArgs &b, int nsrc, u32x4 *dst, size_t nvec,
-                     hipStream_t s, int variant) {
+                     hipStream_t s, int variant, size_t as_bytes) {
     switch (variant) {
       case 0:
         hipLaunchKernelGGL((reduce_tree_vec<OP, T, NLEAF>),
@@ -452,7 +452,7 @@ struct TuneTreeBody {
         return;
       default:
         if (!launch_tree_tune_form<OP, T, NLEAF>(b, nsrc, dst, nvec, s, variant))
-          launch_tree_body<OP, T, NLEAF>(b, nsrc, dst, nvec, s, variant);
+          launch_tree_body<OP, T, NLEAF>(b, nsrc, dst, nvec, s, variant, as_bytes);
     }
   }
 };

@@ -3,7 +3,8 @@
 tests/test_sweep_gpu.py runs every (op, datatype) pair through every tree,
 tree-put and list-form kernel instantiation liblfa.so holds,
 tests/test_sweep_tables_gpu.py every entry of the write, fetch and compare
-tables through its own kernels (the last part of this module);
+tables through its own kernels, tests/test_sweep_forms_gpu.py every form the
+write and tree launchers only take at large sizes (the last parts of this module);
 tests/test_sweep_cpu.py runs the same cases through the host forms and
 checks the conditions below on the inputs themselves.  This module builds the
 cases: the pair lists, operands whose result depends on EVERY input, the byte
@@ -763,3 +764,83 @@ def assert_every_operand_was_odd(table: str, op: int, cases) -> None:
     for path, cands in ODD.items():
         seen = {c.odd for _, c in cases if c.path == path}
         assert seen == {o for o in cands if o in operands_of(table, op)}, (table, op, path, seen)
+
+
+# ----------------------------------------------------- large-size forms ----
+# The forms launch_write and launch_tree_body only take from 32 or 192 MiB per
+# operand (lfa_split.h: lfa_form_write / lfa_form_tree), run at lanes()
+# through the lfa__write_as and lfa__tree_as entries, which choose the form as if the body
+# were `as_bytes` bytes and leave everything else to the real size
+# (tests/test_sweep_forms_gpu.py).  The model below is written from the
+# launchers' table of forms, not from the C functions: tests/test_split_cpu.py
+# holds tools/split_host_check.cpp's output to it.
+
+MIB = 1 << 20
+WRITE_FORMS = ("combine_lds sc1", "combine_lds_taper sc1", "combine_lds nt")    # enum order
+TREE_FORMS = {1: "chunk1 nt", 2: "chunk2 nt", 3: "lds", 11: "chunk2 sc1", 25: "put body"}
+SMALL_FORMS = {"combine_lds sc1", "chunk2 sc1", "chunk2 sc1 +cap", "put body"}
+
+
+def model_write_form(nbytes: int, mapped: bool = False) -> str:
+    """launch_write: the tapered grid from 32 MiB, nt stores (drained) from
+    192 MiB; host-mapped operands keep the small form at every size."""
+    if mapped or nbytes < 32 * MIB:
+        return "combine_lds sc1"
+    return "combine_lds_taper sc1" if nbytes < 192 * MIB else "combine_lds nt"
+
+
+def leaves_of(nsrc: int) -> int:
+    return 1 << (nsrc.bit_length() - 1)
+
+
+def model_tree_form(nbytes: int, nsrc: int, esz: int) -> str:
+    """launch_tree_body: from 192 MiB of output the LDS form at 2 inputs,
+    chunk U=1 at 3..8, chunk U=2 above, all with nt stores; below, the
+    put body at 8..15 inputs of 4-byte or wider elements, else chunk U=2
+    write-through, with the 41 KiB LDS cap at 3..8 inputs."""
+    if nbytes >= 192 * MIB:
+        return "lds" if nsrc == 2 else "chunk1 nt" if nsrc <= 8 else "chunk2 nt"
+    if leaves_of(nsrc) == 8 and esz >= 4:
+        return "put body"
+    return "chunk2 sc1 +cap" if 3 <= nsrc <= 8 else "chunk2 sc1"
+
+
+def model_taper(nvec: int, div: int, hv: int = 1024, tv: int = 256):
+    """lfa_split_taper: (head workgroups, whole tail workgroups, vectors in
+    the last, partial one)."""
+    split = (nvec - nvec // div) // hv * hv
+    return split // hv, (nvec - split) // tv, (nvec - split) % tv
+
+
+FORM_PATHS = ("vec", "head")        # the paths with a vector body
+WRITE_AS = (("combine_lds_taper sc1", 32 * MIB), ("combine_lds nt", 192 * MIB))
+TREE_AS = 192 * MIB
+# the large-only tree instantiation each fan-in of TREE_NSRC reaches
+TREE_AS_FORMS = {2: "lds", 3: "chunk1 nt", 5: "chunk1 nt", 8: "chunk1 nt", 9: "chunk2 nt",
+                 17: "chunk2 nt", 32: "chunk2 nt"}
+
+
+def write_form_cases(op, dts, rng):
+    """(form, as_bytes, dt, TableCase): every type of the op on the vec and
+    head paths, under the tapered and under the nt-drained write body."""
+    for form, as_bytes in WRITE_AS:
+        for dt, case in write_cases(op, dts, rng, FORM_PATHS):
+            yield form, as_bytes, dt, case
+
+
+def tree_form_cases(op, dt, rng):
+    """(form, as_bytes, Case): each fan-in of TREE_NSRC on the vec path, and
+    with the output aliasing the highest input and input 0.  (On the head
+    path the tree takes the element kernel for the whole buffer.)"""
+    esz = esz_of(dt)
+    for nsrc in TREE_NSRC:
+        data = inputs(op, dt, nsrc, lanes(esz), rng)
+        want = reference(op, dt, data)
+        for alias in (None,) + TREE_ALIAS:
+            yield TREE_AS_FORMS[nsrc], TREE_AS, carve(
+                dt, data, want, "vec", alias=alias,
+                what=f"tree as {TREE_AS_FORMS[nsrc]} op={op} dt={dt} nsrc={nsrc} out is {alias}")
+
+
+def n_tree_form_cases(op) -> int:
+    return len(dts_of(op)) * len(TREE_NSRC) * (1 + len(TREE_ALIAS))

@@ -1,14 +1,18 @@
 """lfa_split.h without a GPU: tools/split_host_check.cpp, compiled by g++
 against the header, prints the path and the head / nvec / body / tail split of
 a grid of buffers and the taper split around its tile boundaries; the same
-quantities are computed here from tests/_iov_layout.py's classification.  The
-program is built once more with ASan + UBSan and run stand-alone."""
+quantities are computed here from tests/_iov_layout.py's classification.  It
+also prints the form launch_write and launch_tree_body pick by size (lfa_form_*), with and without
+an as_bytes override, which is held to tests/_sweep.py's model of the
+launchers' table.  The program is built once more with ASan + UBSan and run
+stand-alone."""
 import os
 import subprocess
 
 import pytest
 
 from tests import _iov_layout as L
+from tests import _sweep as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tools", "split_host_check.cpp")
@@ -79,6 +83,50 @@ def test_taper_matches_model(lines):
         rest = nvec - split
         assert 0 <= ntail * tv - rest < tv, case    # the tail tiles cover [split, nvec)
         assert rest >= nvec // div, case            # at least the last 1/div is tapered
+
+
+SMALL = 2597 * 16           # the sweep's body (tests/_sweep.py: lanes)
+FORM_SIZES = [SMALL] + [t * S.MIB + d for t in (32, 64, 192) for d in (-16, 0, 16)] + [5 << 30]
+TREE_VARIANT = {"chunk1 nt": (1, 0), "chunk2 nt": (2, 0), "lds": (3, 0), "chunk2 sc1": (11, 0),
+                "chunk2 sc1 +cap": (11, 1), "put body": (25, 0)}
+
+
+def test_forms_match_model(lines):
+    """lfa_form_write / lfa_form_tree against the model in
+    tests/_sweep.py, which is written from the table of forms and calls no C:
+    at 16 bytes either side of 32, 64 and 192 MiB, at the sweep's 40 KiB and
+    at 5 GiB, as the real body and as as_bytes over the 40 KiB body; write
+    mapped and not, the tree at every fan-in 2..32
+    and element size.  Every form appears, and without as_bytes nothing but
+    the small forms below 32 MiB."""
+    rows = [ln[1:] for ln in lines if ln[0] == "form"]
+    seen, keys = set(), set()
+    for kind, *rest in rows:
+        as_bytes, real, *args = (int(x) for x in rest)
+        assert real == SMALL if as_bytes else real in FORM_SIZES, rest
+        nbytes = as_bytes or real
+        if kind == "write":
+            mapped, got = args
+            form = S.model_write_form(nbytes, bool(mapped))
+            assert S.WRITE_FORMS[got] == form, rest
+        else:
+            nsrc, nleaf, esz, variant, cap = args
+            assert kind == "tree" and nleaf == S.leaves_of(nsrc) and nleaf <= nsrc < 2 * nleaf
+            form = S.model_tree_form(nbytes, nsrc, esz)
+            assert (variant, cap) == TREE_VARIANT[form], rest
+            assert S.TREE_FORMS[variant] == form.replace(" +cap", ""), rest
+        if not as_bytes and real < 32 * S.MIB:
+            assert form in S.SMALL_FORMS, rest
+        seen.add(form)
+        keys.add((kind, bool(as_bytes), nbytes, *args[:-1 if kind != "tree" else -2]))
+    assert seen == set(S.WRITE_FORMS) | set(TREE_VARIANT)
+    # the grid the program walks
+    for forced in (False, True):
+        for nbytes in FORM_SIZES:
+            assert {("write", forced, nbytes, m) for m in (0, 1)} <= keys
+            assert {("tree", forced, nbytes, nsrc, S.leaves_of(nsrc), esz)
+                    for nsrc in range(2, 33) for esz in (1, 2, 4, 8, 16)} <= keys
+    assert len(rows) == 2 * len(FORM_SIZES) * (2 + 31 * 5)
 
 
 def test_split_check_under_sanitizers(tmp_path, lines):

@@ -16,6 +16,10 @@
    and a fetch changes dst, the edge pairs that separate a compare of bits from
    one of values, and the full case list through lfa_host_write,
    lfa_host_readwrite and lfa_host_swap.
+4. The forced large-size forms (tests/test_sweep_forms_gpu.py): the case
+   counts, the form tests/_sweep.py's model names for each as_bytes, the tile
+   shapes lanes() gives the tapered grids and the tree bodies, and the case
+   list through the host forms.
 """
 import ctypes
 import json
@@ -381,3 +385,82 @@ def test_table_check_sees_its_faults():
         case.view(bad, "res")[:] = case.want
         with pytest.raises(AssertionError, match="res is not the old dst"):
             case.check(dt, bad)
+
+
+# ----------------------------------------------------- large-size forms ----
+# tests/test_sweep_forms_gpu.py's cases: (pairs on the vec path, on the head
+# path) per forced form, from the pair lists above
+N_WRITE_FORM_CASES = 2 * (148 + 126)            # taper and nt, every write pair
+N_TREE_FORM_CASES = 133 * 7 * 3                 # 7 fan-ins, plain and two aliasings
+
+
+def test_form_shapes():
+    """lanes() at the forced forms: the body (2597 or 2598 vectors on the vec
+    path, 2600 of 16-byte elements, 2596 or 2597 behind an element head) gives the write taper (last 1/8) 2 whole
+    4-KiB-per-wave head workgroups, 2 whole tail workgroups and a partial
+    one, and the tree bodies 10 (256-vector workgroups: LDS form, chunk
+    U = 1) or 5 (512: chunk U = 2) whole workgroup tiles and a partial one."""
+    for esz in (1, 2, 4, 8, 16):
+        n = S.lanes(esz)
+        bodies = [n * esz // 16] + ([(n * esz - (16 - esz)) // 16] if esz < 16 else [])
+        assert all(2596 <= nvec <= 2600 for nvec in bodies), (esz, bodies)
+        for nvec in bodies:
+            assert (nvec // 256, nvec // 512) == (10, 5) and nvec % 256 and nvec % 512
+            nhead, whole, part = S.model_taper(nvec, 8)
+            assert (nhead, whole) == (2, 2) and 0 < part < 256 and part % 64
+
+
+def test_form_case_lists(manifest):
+    """The forced-form generators: their counts, the form the model names
+    for each as_bytes, and that every large-only form of the table is among
+    them; forced sizes are the thresholds themselves."""
+    wp = S.write_pairs(manifest)
+    rng = np.random.default_rng(1)
+    forms = set()
+    total = 0
+    for op in S.WRITE_OPS:
+        for form, as_bytes, dt, case in S.write_form_cases(op, S.table_dts(wp, op), rng):
+            assert S.model_write_form(as_bytes) == form and case.path in S.FORM_PATHS
+            assert S.model_write_form(as_bytes - 16) != form
+            forms.add(form)
+            total += 1
+    assert total == N_WRITE_FORM_CASES == 548
+    assert sum(S.n_tree_form_cases(op) for op in OPS) == N_TREE_FORM_CASES == 2793
+    for nsrc, form in S.TREE_AS_FORMS.items():
+        for esz in (1, 2, 4, 8, 16):
+            assert S.model_tree_form(S.TREE_AS, nsrc, esz) == form
+            assert S.model_tree_form(S.TREE_AS - 16, nsrc, esz) in S.SMALL_FORMS
+        forms.add((form, S.leaves_of(nsrc)))
+    assert tuple(S.TREE_AS_FORMS) == S.TREE_NSRC
+    # one fan-in per large-only tree instantiation, both large write forms
+    assert forms == {"combine_lds_taper sc1", "combine_lds nt", ("lds", 2), ("chunk1 nt", 2), ("chunk1 nt", 4),
+                     ("chunk1 nt", 8), ("chunk2 nt", 8), ("chunk2 nt", 16), ("chunk2 nt", 32)}
+
+
+@pytest.mark.parametrize("op", S.WRITE_OPS)
+def test_host_write_form_cases(op, manifest):
+    """The forced-form cases through the host forms, which have no forms:
+    this checks the cases and the check, as the host sweeps above do."""
+    dts = S.table_dts(S.write_pairs(manifest), op)
+    ran = 0
+    for _, _, dt, case in S.write_form_cases(op, dts, np.random.default_rng(17000 + op)):
+        a = case.arena.copy()
+        atomic.host_write(op, dt, case.view(a, "dst"), case.view(a, "src"),
+                          S.lanes(S.esz_of(dt)))
+        case.check(dt, a)
+        ran += 1
+    assert ran == 2 * S.n_table_cases(dts, S.FORM_PATHS)
+
+
+@pytest.mark.parametrize("op", OPS)
+def test_host_tree_form_cases(op):
+    rng = np.random.default_rng(12000 + op)
+    ran = 0
+    for dt in S.dts_of(op):
+        for _, _, case in S.tree_form_cases(op, dt, rng):
+            a = case.arena.copy()
+            atomic.host_reduce_tree(op, dt, _view(a, case.outs[0]),
+                                    [_view(a, s) for s in case.ins], S.lanes(S.esz_of(dt)))
+            case.check(dt, a)
+            ran += 1
+    assert ran == S.n_tree_form_cases(op) == 21 * len(S.dts_of(op))

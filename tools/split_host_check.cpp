@@ -1,8 +1,10 @@
 // split_host_check.cpp — lfa_split.h on the host, as g++ sees it: prints the
 // path and the head / nvec / body / tail split of a grid of (element size,
 // dst offset, src offset, count) cases and the taper split around its tile
-// boundaries, one line each, for tests/test_split_cpu.py to compare with the
-// same quantities computed in Python.  Also built with ASan + UBSan:
+// boundaries, and the form launch_write and launch_tree_body pick by size
+// (lfa_form_write, lfa_form_tree) around every threshold, with and without an
+// as_bytes override, one line each, for tests/test_split_cpu.py to compare with
+// the same quantities computed in Python.  Also built with ASan + UBSan:
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all
 //       tools/split_host_check.cpp -o /tmp/split_host_check && /tmp/split_host_check
@@ -45,6 +47,32 @@ int main() {
           const struct lfa_taper t = lfa_split_taper(nvec, div, 4096, tv);
           printf("taper %zu %zu %zu %zu %u %u\n", nvec, div, tv, t.split, t.nhead, t.ntail);
         }
+    }
+  // The form each launcher picks by size (lfa_form_*): body sizes 16 bytes
+  // either side of every threshold, one small and one huge, first as the
+  // real body (as_bytes 0), then as as_bytes over a small real body.
+  size_t sizes[11], nsize = 0;
+  const size_t small = (size_t)2597 * 16;
+  sizes[nsize++] = small;
+  static const size_t mibs[] = {32, 64, 192};
+  for (size_t mib : mibs)
+    for (size_t d = 0; d <= 32; d += 16) sizes[nsize++] = (mib << 20) - 16 + d;
+  sizes[nsize++] = (size_t)5 << 30;
+  for (int forced = 0; forced <= 1; forced++)
+    for (size_t i = 0; i < nsize; i++) {
+      const size_t real = forced ? small : sizes[i], as = forced ? sizes[i] : 0;
+      const size_t bytes = lfa_form_bytes(real / 16, as);
+      for (int mapped = 0; mapped <= 1; mapped++)
+        printf("form write %zu %zu %d %d\n", as, real, mapped, (int)lfa_form_write(bytes, mapped));
+      for (int nsrc = 2; nsrc <= 32; nsrc++) {
+        int nleaf = 1;
+        while (nleaf * 2 <= nsrc) nleaf *= 2;
+        for (size_t esz : esz_all) {
+          const struct lfa_tree_form f = lfa_form_tree(bytes, nsrc, nleaf, esz);
+          printf("form tree %zu %zu %d %d %zu %d %d\n", as, real, nsrc, nleaf, esz, f.variant,
+                 f.cap_lds);
+        }
+      }
     }
   return 0;
 }
