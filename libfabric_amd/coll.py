@@ -418,6 +418,22 @@ def oneshot_reduce(op: int, dt: int, a: OneShot, stream) -> None:
          "lfa_oneshot_reduce_async")
 
 
+def oneshot_reduce_as(op: int, dt: int, a: OneShot, stream, ll: int) -> None:
+    """lfa__oneshot_as (liblfa.so, test-only): oneshot_reduce with the kernel
+    chosen per call.  ll < 0: the launcher's own choice (LFA_OS_LL); 0: the
+    flagged kernel; 1: the LL kernel, CollError(-LFA_EINVAL) where the launcher
+    never takes it (one member, a part above LFA_OS_LL_BYTES, reduce to a root)."""
+    L = _lib()
+    if not getattr(L, "_oneshot_as_bound", False):
+        L.lfa__oneshot_as.restype = ctypes.c_int
+        L.lfa__oneshot_as.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(OneShot),
+                                      ctypes.c_void_p, ctypes.c_int]
+        L._oneshot_as_bound = True
+    h = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    _chk(L.lfa__oneshot_as(op, dt, ctypes.byref(a), ctypes.c_void_p(h), ll),
+         f"lfa__oneshot_as(ll={ll})")
+
+
 class Endpoint:
     """One rank's domain + endpoint.  Buffers: torch tensors (device or host)
     or numpy arrays (host).  Calls return after enqueueing; completions come

@@ -258,12 +258,29 @@ int lfa_reduce_tree_put_async(enum lfa_op op, enum lfa_datatype dt,
   return kOps[op]->treeput(dt, dsts, ndst, srcs, nsrc, cnt, stream);
 }
 
-int lfa_oneshot_reduce_async(int op, int dt, const struct lfa_oneshot *a,
-                                void *stream) {
+// The one-shot launch shares its validation with the lfa__oneshot_as entry
+// below, which differs only in passing ll on.
+static int oneshot_as(int op, int dt, const struct lfa_oneshot *a, void *stream, int ll) {
   if ((unsigned)op > LFA_BXOR || !reducible(op, dt))
     return -LFA_EOPNOTSUPP;
   if (!a) return -LFA_EINVAL;
-  return kOps[op]->oneshot(dt, a, stream);
+  return kOps[op]->oneshot(dt, a, stream, ll);
+}
+
+int lfa_oneshot_reduce_async(int op, int dt, const struct lfa_oneshot *a,
+                                void *stream) {
+  return oneshot_as(op, dt, a, stream, -1);
+}
+
+// Test-only entry (internal, as lfa__write_as; not in include/): the one-shot
+// launch with the kernel chosen per call instead of by LFA_OS_LL, which a
+// process reads once, so that tests/test_sweep_oneshot_gpu.py runs both
+// kernels in one process.  ll < 0: the launcher's own choice; 0: the flagged
+// kernel; 1: the LL kernel, or -LFA_EINVAL where the launcher's rule forbids it
+// apart from the environment (one member, a part above LFA_OS_LL_BYTES, reduce
+// to a root): never a silent fall-back.
+int lfa__oneshot_as(int op, int dt, const struct lfa_oneshot *a, void *stream, int ll) {
+  return oneshot_as(op, dt, a, stream, ll < 0 ? -1 : ll > 0);
 }
 
 }  // extern "C"

@@ -193,10 +193,10 @@ static int op_tree(int dt, void *dst, const void *const *srcs, int nsrc, size_t 
   });
 }
 
-static int op_oneshot(int dt, const lfa_oneshot *a, void *stream) {
+static int op_oneshot(int dt, const lfa_oneshot *a, void *stream, int ll) {
   return lfa::by_reduce_type<LFA_OP>(dt, [&](auto *tag) {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
-    return lfa::launch_oneshot<LFA_OP, T>(*a, (hipStream_t)stream);
+    return lfa::launch_oneshot<LFA_OP, T>(*a, (hipStream_t)stream, ll);
   });
 }
 

@@ -391,8 +391,13 @@ static inline size_t os_min_chunk() {
   return (size_t)c;
 }
 
+// ll: which kernel (the lfa__oneshot_as test entry, lfa_capi.cpp).  < 0, every
+// product caller: ll_enabled() decides; 0: the flagged kernel; 1: the LL
+// kernel, -LFA_EINVAL where the rule below forbids it whatever the environment
+// says (n == 1, a part above LFA_OS_LL_BYTES, reduce to a root), before the
+// first HIP call.  Grid, chunk and arguments do not depend on it.
 template <int OP, typename T>
-static int launch_oneshot(const lfa_oneshot &h, hipStream_t s) {
+static int launch_oneshot(const lfa_oneshot &h, hipStream_t s, int ll = -1) {
   if constexpr (!supported<OP, T>()) {
     return -LFA_EOPNOTSUPP;
   } else {
@@ -428,6 +433,9 @@ static int launch_oneshot(const lfa_oneshot &h, hipStream_t s) {
       return -LFA_EINVAL;
     for (int k = 0; k < n && n > 1; k++)
       if (!h.sym[k] || (uintptr_t)h.sym[k] % 256) return -LFA_EINVAL;
+    const bool ll_ok = n > 1 && most <= LFA_OS_LL_BYTES &&
+                       (h.mode == LFA_ONESHOT_ALL || h.mode == LFA_ONESHOT_SCATTER);
+    if (ll > 0 && !ll_ok) return -LFA_EINVAL;
     const void *srcs[kOsMax];
     const size_t par = (size_t)(h.epoch & 1) * h.parity_off;
     uintptr_t mis = (uintptr_t)h.result % 16;
@@ -447,8 +455,7 @@ static int launch_oneshot(const lfa_oneshot &h, hipStream_t s) {
       a.t.hi[k] = tree.hi[k];
       a.t.lo[k] = tree.lo[k];
     }
-    if (n > 1 && most <= LFA_OS_LL_BYTES &&
-        (h.mode == LFA_ONESHOT_ALL || h.mode == LFA_ONESHOT_SCATTER) && ll_enabled()) {
+    if (ll_ok && (ll < 0 ? ll_enabled() : ll > 0)) {
       // LL one-shot: the words live in the flag area (lfa_signal.h)
       LlArgs l;
       memset(&l, 0, sizeof(l));

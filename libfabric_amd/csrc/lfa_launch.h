@@ -9,7 +9,9 @@
  * `stream` a hipStream_t.  write and tree end in `as_bytes`: 0 from every
  * product caller; otherwise the vector body's form is chosen as if the body
  * were that many bytes (lfa_split.h; the lfa__write_as / lfa__tree_as test
- * entries).
+ * entries).  oneshot ends in `ll`: -1 from every product caller (the
+ * launcher's own choice of kernel); 0 the flagged kernel, 1 the LL kernel (the
+ * lfa__oneshot_as test entry).
  */
 #ifndef LFA_LAUNCH_H
 #define LFA_LAUNCH_H
@@ -31,7 +33,7 @@ typedef int (*lfa_launch_treev_t)(int dt, const struct lfa_iov_args *a, int nsrc
                                   unsigned ntile, void *stream);
 typedef int (*lfa_launch_treeput_t)(int dt, void *const *dsts, int ndst, const void *const *srcs,
                                     int nsrc, size_t cnt, void *stream);
-typedef int (*lfa_launch_oneshot_t)(int dt, const struct lfa_oneshot *a, void *stream);
+typedef int (*lfa_launch_oneshot_t)(int dt, const struct lfa_oneshot *a, void *stream, int ll);
 typedef int (*lfa_launch_readwrite_t)(int dt, void *dst, const void *src, void *res, size_t cnt,
                                       void *stream);
 typedef int (*lfa_launch_swap_t)(int dt, void *dst, const void *src, const void *cmp, void *res,

@@ -4,7 +4,8 @@ tests/test_sweep_gpu.py runs every (op, datatype) pair through every tree,
 tree-put and list-form kernel instantiation liblfa.so holds,
 tests/test_sweep_tables_gpu.py every entry of the write, fetch and compare
 tables through its own kernels, tests/test_sweep_forms_gpu.py every form the
-write and tree launchers only take at large sizes (the last parts of this module);
+write and tree launchers only take at large sizes, tests/test_sweep_oneshot_gpu.py
+every one-shot kernel, one rank at a time (the last parts of this module);
 tests/test_sweep_cpu.py runs the same cases through the host forms and
 checks the conditions below on the inputs themselves.  This module builds the
 cases: the pair lists, operands whose result depends on EVERY input, the byte
@@ -844,3 +845,415 @@ def tree_form_cases(op, dt, rng):
 
 def n_tree_form_cases(op) -> int:
     return len(dts_of(op)) * len(TREE_NSRC) * (1 + len(TREE_ALIAS))
+
+
+# ------------------------------------------------------------- one-shot ----
+# The one-shot kernels (lfa_k_oneshot.hpp): oneshot_reduce<OP, T, 1|2|4|8> and
+# oneshot_ll<OP, T, 2|4|8>, run one rank at a time on one stream
+# (tests/test_sweep_oneshot_gpu.py).  Rank r's kernel waits only on its own
+# workspace, so with the flags posted beforehand it never has to wait, and
+# what it pushed and posted can be read back.  Below: a model of the layout in
+# lfa_signal.h and launch_oneshot (tests/test_sweep_cpu.py holds the constants
+# to the header's text), the case builder, the protocol (os_run) over a
+# `dev` that holds the buffers, and OsEmu, a numpy dev that emulates push,
+# post, wait and reduce, so the protocol is proved before it meets a kernel.
+
+OS_ALL, OS_SCATTER = -1, -2         # struct lfa_oneshot's mode; >= 0: reduce to that root
+FLAG, LL = "flag", "ll"             # the kernels; lfa__oneshot_as's ll argument below
+OS_LL_ARG = {FLAG: 0, LL: 1}
+SIG_MAX, SIG_AREA, SIG_OS_OFF, SIG_OS_CHUNKS, OS_MAX_RANKS = 32, 1 << 20, 256, 128, 8
+LL_BYTES = 16 << 10
+LL_SLOT, LL_PARITY, LL_OFF = 2 * LL_BYTES, 8 * 2 * LL_BYTES, 64 << 10
+OS_MIN_CHUNK = 4096
+SIG_NONE = 0xFFFFFFFFFFFFFFFF
+WS_FILL = 0xA5                      # a workspace byte nothing wrote
+LL_JUNK = 0x5EED1E55                # the data word of an LL pair nothing pushed
+OS_TIMEOUT_US = 2_000_000           # a guard no correct run reaches
+OS_NLEAF = {FLAG: (1, 2, 4, 8), LL: (2, 4, 8)}
+N_OS_INSTANCES = 133 * (4 + 3)      # the instantiations launch_oneshot chooses among
+
+
+def os_parts(mode: int, n: int, count: int, esz: int):
+    """(soff, slen) in bytes: the range of every rank's input that member k
+    reduces (launch_oneshot; SCATTER is lfa_coll_block's partition)."""
+    if mode == OS_SCATTER:
+        base, extra = divmod(count, n)
+        return ([(k * base + min(k, extra)) * esz for k in range(n)],
+                [(base + (k < extra)) * esz for k in range(n)])
+    return [0] * n, [count * esz if mode in (OS_ALL, k) else 0 for k in range(n)]
+
+
+def os_grid(kernel: str, most: int):
+    """(chunk, workgroups) for a largest part of `most` bytes.  Flagged: at
+    most LFA_SIG_OS_CHUNKS chunks, a multiple of 16, never below 4096.  LL:
+    16 bytes per lane, 256 lanes per workgroup (chunk is None)."""
+    if kernel == LL:
+        return None, -(-(-(-most // 16)) // 256)
+    chunk = max((-(-most // SIG_OS_CHUNKS) + 15) // 16 * 16, OS_MIN_CHUNK)
+    return chunk, -(-most // chunk)
+
+
+def os_offsets(esz: int, path: str, flip: int = 0):
+    """(send, result) byte offsets past a 16-byte boundary.  vec: both
+    aligned; head: both one element on; elem: one of them one element on
+    (which: flip); bytes: one of them one byte off the element."""
+    assert path in paths_of(esz), (esz, path)
+    if path == "vec":
+        return 0, 0
+    if path == "head":
+        return esz, esz
+    d = esz if path == "elem" else 1
+    return (0, d) if flip % 2 == 0 else (d, 0)
+
+
+def ll_pack(part: np.ndarray, flag: int, fill: int = 0) -> np.ndarray:
+    """A part as the LL kernel pushes it: zero-padded to 16 bytes, every 4
+    bytes followed by the flag word."""
+    pad = np.full(-(-part.size // 16) * 16, fill, np.uint8)
+    pad[:part.size] = part
+    w = np.empty((pad.size // 4, 2), np.uint32)
+    w[:, 0], w[:, 1] = pad.view(np.uint32), flag
+    return w.reshape(-1).view(np.uint8)
+
+
+def ll_unpack(words: np.ndarray):
+    """(data bytes, flag words) of LL pairs."""
+    w = np.ascontiguousarray(words).view(np.uint32).reshape(-1, 2)
+    return np.ascontiguousarray(w[:, 0]).view(np.uint8), w[:, 1].copy()
+
+
+class OsCase:
+    """One one-shot operation of n ranks: every rank's send and result carved
+    from one arena (`sends[r]`, `results[r]`: (start, bytes), or None for a
+    rank without a result), the smallest legal workspaces, and `want[r]`: the
+    bytes rank r's result must hold."""
+
+    def __init__(self, op, dt, n, mode, count, kernel, path, epoch, data, flip=0, done=False,
+                 ll=None, what=""):
+        esz = esz_of(dt)
+        assert 1 <= n <= OS_MAX_RANKS and all(x.size == count * esz for x in data)
+        self.op, self.dt, self.n, self.mode, self.count = op, dt, n, mode, count
+        self.kernel, self.path, self.epoch, self.done = kernel, path, epoch & 0xFFFFFFFF, done
+        self.ll = OS_LL_ARG[kernel] if ll is None else ll
+        self.soff, self.slen = os_parts(mode, n, count, esz)
+        self.most = max(self.slen)
+        assert kernel == FLAG or (n > 1 and self.most <= LL_BYTES and mode < 0)
+        self.chunk, self.grid = os_grid(kernel, self.most)
+        self.nleaf = leaves_of(n)
+        # lfa_signal.h: a slot is the largest part rounded up to 256; the odd
+        # epochs' slots lie parity_off above the even ones; then the flag area
+        self.slot_bytes = -(-self.most // 256) * 256
+        self.parity_off = n * self.slot_bytes
+        self.flag_off = 2 * self.parity_off
+        self.ws_bytes = self.flag_off + SIG_AREA if n > 1 else 0
+        self.flag = (2 * self.epoch + 1) & 0xFFFFFFFF
+        s_off, r_off = os_offsets(esz, path, flip)
+        has = [r for r in range(n) if self.slen[r]]
+        self.segs, size = L.plan([count * esz] * n + [self.slen[r] for r in has],
+                                 [s_off] * n + [r_off] * len(has), 1)
+        self.sends = self.segs[:n]
+        self.results = [None] * n
+        for r, seg in zip(has, self.segs[n:]):
+            self.results[r] = seg
+        self.arena = np.full(size, L.SENTINEL, np.uint8)
+        for (lo, nb), x in zip(self.sends, data):
+            self.arena[lo:lo + nb] = x
+        for r in has:
+            lo, nb = self.results[r]
+            self.arena[lo:lo + nb] = OUT_FILL
+        full = data[0] if n == 1 else reference(op, dt, data)      # one rank: a copy
+        self.want = [full[self.soff[r]:self.soff[r] + self.slen[r]] if self.slen[r] else None
+                     for r in range(n)]
+        # what launch_oneshot derives from the addresses (the arena is 16-B aligned)
+        self.unal = bool(s_off % esz or (has and r_off % esz))
+        mis = any((s_off + o) % 16 for o in self.soff) or bool(has and r_off % 16)
+        self.vec = not mis and (kernel == LL or not self.unal)
+        self.what = what or (f"oneshot {kernel} op={op} dt={dt} n={n} mode={mode} count={count} "
+                             f"{path} epoch={self.epoch:#x}")
+
+    # ---- where things live in member j's workspace (bytes) ----
+    def slot_at(self, k: int) -> int:
+        return (self.epoch & 1) * self.parity_off + k * self.slot_bytes
+
+    def flag_at(self, b: int, k: int) -> int:
+        return self.flag_off + SIG_OS_OFF + 4 * (b * SIG_MAX + k)
+
+    def ll_slot_at(self, k: int) -> int:
+        return self.flag_off + LL_OFF + (self.epoch & 1) * LL_PARITY + k * LL_SLOT
+
+    def send_part(self, r: int, k: int) -> np.ndarray:
+        """The bytes of rank r's input that member k reduces."""
+        lo = self.sends[r][0] + self.soff[k]
+        return self.arena[lo:lo + self.slen[k]]
+
+    def preposted(self, ws: np.ndarray) -> None:
+        """Fill the members' workspaces (back to back in ws) as before the
+        first launch: WS_FILL, and the flags every wait of this epoch accepts
+        (flagged: every one-shot flag word epoch + 1, which a kernel's own
+        post of `epoch` stays distinguishable from; LL: every pair of this
+        parity's slots {junk, 2·epoch + 1})."""
+        ws[:] = WS_FILL
+        for j in range(self.n if self.ws_bytes else 0):
+            m = ws[j * self.ws_bytes:(j + 1) * self.ws_bytes]
+            if self.kernel == FLAG:
+                lo = self.flag_at(0, 0)
+                m[lo:lo + 4 * SIG_OS_CHUNKS * SIG_MAX].view(np.uint32)[:] = \
+                    (self.epoch + 1) & 0xFFFFFFFF
+            else:
+                lo = self.ll_slot_at(0)
+                w = m[lo:lo + LL_PARITY].view(np.uint32).reshape(-1, 2)
+                w[:, 0], w[:, 1] = LL_JUNK, self.flag
+
+    def windows(self):
+        """[(start in the back-to-back workspaces, expected bytes, what)]:
+        everything one pass of all ranks writes into the workspaces."""
+        out = []
+        for j in range(self.n if self.ws_bytes else 0):
+            base = j * self.ws_bytes
+            for r in range(self.n):
+                if r == j or not self.slen[j]:
+                    continue
+                part = self.send_part(r, j)
+                if self.kernel == FLAG:
+                    out.append((base + self.slot_at(r), part.copy(), f"slot {r} at member {j}"))
+                else:
+                    out.append((base + self.ll_slot_at(r), ll_pack(part, self.flag),
+                                f"LL slot {r} at member {j}"))
+            if self.kernel == FLAG:
+                rows = np.full((self.grid, SIG_MAX), (self.epoch + 1) & 0xFFFFFFFF, np.uint32)
+                for r in range(self.n):
+                    if r != j:
+                        rows[:, r] = self.epoch
+                out.append((base + self.flag_at(0, 0), rows.reshape(-1).view(np.uint8),
+                            f"flag rows of member {j}"))
+        return out
+
+    def check(self, got: np.ndarray) -> None:
+        got = np.asarray(got)
+        assert got.shape == self.arena.shape, self.what
+        assert L.gaps_intact(got, self.segs), f"{self.what}: a gap lost its sentinel"
+        for r, (lo, nb) in enumerate(self.sends):
+            assert np.array_equal(got[lo:lo + nb], self.arena[lo:lo + nb]), \
+                f"{self.what}: input {r} changed"
+        for r, seg in enumerate(self.results):
+            if seg is not None:
+                lo, nb = seg
+                assert_same(self.dt, got[lo:lo + nb].copy(), self.want[r],
+                            f"{self.what} rank {r}")
+
+
+def os_run(case: OsCase, dev) -> None:
+    """The protocol.  dev.load(case) uploads the arena and prepares the
+    workspaces as OsCase.preposted does; dev.launch(case, r, done_val)
+    launches rank r's kernel, synchronises and returns (status word, done
+    word, done counter) (the last two None without done_val); dev.gather
+    downloads ranges of the workspaces, dev.untouched says whether everything
+    outside them still holds what load left; dev.refill puts OUT_FILL back
+    into the results; dev.arena downloads the arena."""
+    dev.load(case)
+    for p in (1, 2):
+        # pass 1 pushes and posts (its results are meaningless: early ranks
+        # read slots not pushed yet); pass 2, same epoch, reduces what is there
+        for r in range(case.n):
+            val = (0x0D0E000000000000 | p << 8 | r) if case.done else 0
+            status, word, ctr = dev.launch(case, r, val)
+            assert status == SIG_NONE, f"{case.what}: rank {r} pass {p} timed out ({status:#x})"
+            if case.done:   # the counter reads 0 again: the next launch reuses it
+                assert (word, ctr) == (val, 0), f"{case.what}: rank {r} pass {p} done {word:#x} {ctr}"
+        if p == 2:
+            break
+        wins = case.windows()
+        ranges = [(lo, b.size) for lo, b, _ in wins]
+        got = dev.gather(ranges)
+        at = 0
+        for lo, want, what in wins:
+            g = got[at:at + want.size]
+            at += want.size
+            if not np.array_equal(g, want):
+                i = int(np.nonzero(g != want)[0][0])
+                raise AssertionError(f"{case.what}: {what} differs from byte {i}: got "
+                                     f"{g[i:i + 8].tolist()} want {want[i:i + 8].tolist()}")
+        assert dev.untouched(ranges), \
+            f"{case.what}: a workspace byte outside the expected pushes and posts changed"
+        dev.refill(case)
+    case.check(dev.arena())
+
+
+class OsEmu:
+    """A numpy dev: each launch pushes, posts, waits and reduces as the
+    kernels' comments say, through OsCase's layout.  `fault`: one of
+    OS_FAULTS, to show that os_run sees it."""
+
+    def __init__(self, fault=None):
+        self.fault = fault
+
+    def load(self, c):
+        self.a = c.arena.copy()
+        self.ws = np.empty(c.n * c.ws_bytes, np.uint8)
+        c.preposted(self.ws)
+        self.base = self.ws.copy()
+
+    def _part(self, c, r, k, nb=None):
+        off = c.soff[r if self.fault == "soff_rank" and c.kernel == FLAG else k]
+        lo = c.sends[r][0] + off
+        return self.a[lo:lo + (c.slen[k] if nb is None else nb)]
+
+    def launch(self, c, r, done_val):
+        status, W = SIG_NONE, c.ws_bytes
+        mine = self.ws[r * W:(r + 1) * W]
+        post = (c.epoch - (self.fault == "post_minus_1")) & 0xFFFFFFFF
+        ins = []
+        for k in range(c.n):
+            if k == r:
+                ins.append(self._part(c, r, r).copy())
+                continue
+            peer = self.ws[k * W:(k + 1) * W]
+            if c.kernel == FLAG:
+                lo = c.slot_at(r)
+                peer[lo:lo + c.slen[k]] = self._part(c, r, k)
+                for b in range(c.grid):
+                    peer[c.flag_at(b, r):c.flag_at(b, r) + 4].view(np.uint32)[0] = post
+                    w = int(mine[c.flag_at(b, k):c.flag_at(b, k) + 4].view(np.uint32)[0])
+                    if (w - c.epoch) & 0x80000000:      # the wait's signed compare
+                        status = 1
+                lo = c.slot_at(k)
+                ins.append(mine[lo:lo + c.slen[r]].copy())
+            else:
+                if c.slen[k]:
+                    words = ll_pack(self._part(c, r, k), c.flag,
+                                    0x5A if self.fault == "no_zero_fill" else 0)
+                    lo = c.ll_slot_at(r)
+                    peer[lo:lo + words.size] = words
+                lo = c.ll_slot_at(k)
+                data, flags = ll_unpack(mine[lo:lo + 2 * (-(-c.slen[r] // 16) * 16)])
+                if (flags != c.flag).any():
+                    status = 1
+                ins.append(data[:c.slen[r]].copy())
+        if c.slen[r] and status == SIG_NONE:
+            if self.fault == "leaf0_for_7" and c.n == 8:
+                ins[7] = ins[0]
+            if self.fault == "swap_node" and c.n > c.nleaf:
+                ins[0], ins[1] = ins[1], ins[0]
+            out = ins[0] if c.n == 1 else reference(c.op, c.dt, ins)
+            lo, nb = c.results[r]
+            if self.fault == "vhi_hi" and c.kernel == FLAG and c.vec:
+                nb -= nb % 16
+            self.a[lo:lo + nb] = out[:nb]
+        return status, (done_val if done_val else None), (0 if done_val else None)
+
+    def gather(self, ranges):
+        return np.concatenate([self.ws[lo:lo + nb] for lo, nb in ranges] or
+                              [np.zeros(0, np.uint8)])
+
+    def untouched(self, ranges):
+        d = self.ws != self.base
+        for lo, nb in ranges:
+            d[lo:lo + nb] = False
+        return not d.any()
+
+    def refill(self, c):
+        for seg in c.results:
+            if seg is not None:
+                self.a[seg[0]:seg[0] + seg[1]] = OUT_FILL
+
+    def arena(self):
+        return self.a
+
+
+OS_FAULTS = ("swap_node", "leaf0_for_7", "vhi_hi", "soff_rank", "post_minus_1", "no_zero_fill")
+
+# ---- the cases ----
+# (ranks, mode) per pair: flagged (NLEAF 1, 2, 2, 4, 8; scatter; reduce to a
+# root that is not rank 0) and LL
+OS_ROW_FLAG = ((1, OS_ALL), (2, OS_ALL), (3, OS_ALL), (5, OS_ALL), (8, OS_ALL),
+               (3, OS_SCATTER), (8, OS_SCATTER), (2, 1), (5, 3))
+OS_ROW_LL = ((2, OS_ALL), (3, OS_ALL), (5, OS_ALL), (8, OS_ALL), (3, OS_SCATTER), (8, OS_SCATTER))
+OS_ROWS = {FLAG: OS_ROW_FLAG, LL: OS_ROW_LL}
+OS_FOLD_N = (4, 6, 7)               # tree_leaves' folding at the remaining rank counts
+OS_EPOCHS = (1, 2, 0x7FFFFFFF, 0xFFFFFFFF)
+OS_EPOCH_N = {FLAG: (1, 2, 5, 8), LL: (2, 5, 8)}
+# largest part in bytes before the odd elements: 2 whole 4-KiB workgroups and
+# 80 bytes (flagged: a partial chunk with a vector body and a tail); 9 KiB (LL)
+OS_PART = {FLAG: 2 * 4096 + 80, LL: 9 << 10}
+OS_ODD = 3
+OS_BIG_PART = 128 * 4096 + 4096 + 48        # chunk > 4096: 4144, 128 workgroups
+N_OS_PAIR_CASES = len(OS_ROW_FLAG) + len(OS_ROW_LL)                 # 15 per pair
+# per op: folding, epochs, size edges, completion word
+N_OS_OP_CASES = 3 + 4 * (4 + 3) + 11 + 4                            # 46
+N_OS_CASES = 133 * 15 + 10 * 46                                     # 2455
+
+
+def os_count(kernel: str, mode: int, n: int, esz: int) -> int:
+    """Elements for the rows' shape: the largest part is OS_PART[kernel]
+    bytes plus OS_ODD elements (SCATTER: the last rank's is one shorter)."""
+    per = OS_PART[kernel] // esz + OS_ODD
+    return n * per - 1 if mode == OS_SCATTER else per
+
+
+def os_dt(op: int, salt: int) -> int:
+    """One datatype of the op, another one for another salt."""
+    dts = dts_of(op)
+    return dts[(op + salt) % len(dts)]
+
+
+def _os_case(op, dt, n, mode, count, kernel, path, epoch, rng, **kw):
+    return OsCase(op, dt, n, mode, count, kernel, path, epoch,
+                  inputs(op, dt, n, count, rng), **kw)
+
+
+def os_pair_cases(op, dt, rng):
+    """The 15 cases every pair runs.  The path rotates with the row and with
+    the pair's index in its op, so every pair meets every path its element
+    size has on both kernels and every op meets every (path, NLEAF); the
+    epoch's parity alternates from case to case."""
+    esz = esz_of(dt)
+    paths, i = paths_of(esz), dts_of(op).index(dt)
+    for kernel in (FLAG, LL):
+        for ci, (n, mode) in enumerate(OS_ROWS[kernel]):
+            turn = ci + i
+            yield _os_case(op, dt, n, mode, os_count(kernel, mode, n, esz), kernel,
+                           paths[turn % len(paths)], 10 + turn, rng, flip=turn // len(paths))
+
+
+def os_op_cases(op, rng):
+    """The 46 cases every op runs on one datatype each: the non-power-of-two
+    folding at 4, 6 and 7 ranks; both parities and the epochs around 2^31 and
+    2^32 per (kernel, NLEAF); the size edges; the completion word."""
+    turn = 0
+
+    def case(dt, n, mode, count, kernel, path="vec", epoch=None, **kw):
+        nonlocal turn
+        turn += 1
+        return _os_case(op, dt, n, mode, count, kernel, path,
+                        20 + turn if epoch is None else epoch, rng, **kw)
+    for n in OS_FOLD_N:
+        dt = os_dt(op, n)
+        yield case(dt, n, OS_ALL, os_count(FLAG, OS_ALL, n, esz_of(dt)), FLAG,
+                   paths_of(esz_of(dt))[n % len(paths_of(esz_of(dt)))])
+    for ki, kernel in enumerate((FLAG, LL)):
+        for n in OS_EPOCH_N[kernel]:
+            dt = os_dt(op, 10 * ki + n)
+            for epoch in OS_EPOCHS:
+                yield case(dt, n, OS_ALL, os_count(kernel, OS_ALL, n, esz_of(dt)), kernel,
+                           epoch=epoch)
+    dt = os_dt(op, 7)
+    esz = esz_of(dt)
+    for kernel, n in ((FLAG, 1), (FLAG, 3), (LL, 3)):               # one element
+        yield case(dt, n, OS_ALL, 1, kernel)
+    for kernel in (FLAG, LL):       # empty blocks: the last rank has no result
+        for n in (3, 8):
+            yield case(dt, n, OS_SCATTER, n - 1, kernel)
+    yield case(dt, 2, OS_ALL, LL_BYTES // esz, LL)                  # the largest LL part
+    yield case(dt, 2, OS_ALL, LL_BYTES // esz + 1, FLAG)            # one element above it
+    for n in (2, 3):
+        yield case(dt, n, OS_ALL, OS_BIG_PART // esz, FLAG)
+    for ki, kernel in enumerate((FLAG, LL)):                        # completion word
+        dt = os_dt(op, 3 + ki)
+        for count in (256 // esz_of(dt) + OS_ODD, os_count(kernel, OS_ALL, 2, esz_of(dt))):
+            yield case(dt, 2, OS_ALL, count, kernel, done=True)
+
+
+def os_cases(op, rng):
+    for dt in dts_of(op):
+        yield from os_pair_cases(op, dt, rng)
+    yield from os_op_cases(op, rng)

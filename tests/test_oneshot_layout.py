@@ -10,15 +10,16 @@ import ctypes
 import pytest
 
 from libfabric_amd import coll
-from libfabric_amd.atomic import LFA_EINVAL
+from libfabric_amd.atomic import LFA_EINVAL, LFA_EOPNOTSUPP
 
 FI_SUM, FI_FLOAT = 2, 8
+LL_BYTES = 16 << 10                  # lfa_signal.h LFA_OS_LL_BYTES
 BASE = 1 << 30                       # never dereferenced: every case is refused
 
 
-def _args(n=4, count=1024, slot=4096, parity_off=1 << 20, sym_align=0):
+def _args(n=4, count=1024, slot=4096, parity_off=1 << 20, sym_align=0, mode=-1):
     sym = (ctypes.c_void_p * n)(*[BASE + k * (4 << 20) + sym_align for k in range(n)])
-    a = coll.OneShot(BASE - (1 << 20), BASE - (2 << 20), count, -1,
+    a = coll.OneShot(BASE - (1 << 20), BASE - (2 << 20), count, mode,
                      ctypes.cast(sym, ctypes.c_void_p), slot, parity_off, 2 << 20, n, 0, 1,
                      BASE - (3 << 20), 1, 1000)
     return a, sym
@@ -36,6 +37,39 @@ def test_layout_refused(kw):
     a, _sym = _args(**kw)
     with pytest.raises(coll.CollError) as e:
         coll.oneshot_reduce(FI_SUM, FI_FLOAT, a, None)
+    assert e.value.rc == -LFA_EINVAL
+
+
+@pytest.mark.parametrize("ll", [-1, 0, 1])
+@pytest.mark.parametrize("kw", [dict(parity_off=0), dict(slot=2048), dict(sym_align=16)])
+def test_oneshot_as_validation_is_the_public_entry(kw, ll):
+    """lfa__oneshot_as (test-only: the kernel chosen per call) refuses what
+    lfa_oneshot_reduce_async refuses, whatever ll says."""
+    a, _sym = _args(**kw)
+    with pytest.raises(coll.CollError) as e:
+        coll.oneshot_reduce_as(FI_SUM, FI_FLOAT, a, None, ll)
+    assert e.value.rc == -LFA_EINVAL
+    with pytest.raises(coll.CollError) as e:
+        coll.oneshot_reduce_as(11, FI_FLOAT, a, None, ll)       # ATOMIC_WRITE does not reduce
+    assert e.value.rc == -LFA_EOPNOTSUPP
+    with pytest.raises(coll.CollError) as e:
+        coll.oneshot_reduce(11, FI_FLOAT, a, None)
+    assert e.value.rc == -LFA_EOPNOTSUPP
+
+
+@pytest.mark.parametrize("kw", [
+    dict(n=1, mode=-1),                         # one member: nothing to exchange
+    dict(count=LL_BYTES // 4 + 1, slot=LL_BYTES + 256, mode=-1),    # a part above LFA_OS_LL_BYTES
+    dict(count=4 * (LL_BYTES // 4) + 4, slot=LL_BYTES + 256, mode=-2),  # scatter: a block above it
+    dict(mode=0), dict(mode=3),                 # reduce to a root: the flagged kernel only
+])
+def test_oneshot_as_refuses_ll_where_the_launcher_never_takes_it(kw):
+    """ll = 1 where launch_oneshot's rule forbids the LL kernel apart from the
+    environment switch: -LFA_EINVAL before the first HIP call (these pointers
+    are never dereferenced), not a silent fall-back to the flagged kernel."""
+    a, _sym = _args(**kw)
+    with pytest.raises(coll.CollError) as e:
+        coll.oneshot_reduce_as(FI_SUM, FI_FLOAT, a, None, 1)
     assert e.value.rc == -LFA_EINVAL
 
 

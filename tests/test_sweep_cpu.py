@@ -20,10 +20,16 @@
    counts, the form tests/_sweep.py's model names for each as_bytes, the tile
    shapes lanes() gives the tapered grids and the tree bodies, and the case
    list through the host forms.
+5. The one-shot sweep (tests/test_sweep_oneshot_gpu.py): the layout model
+   against lfa_signal.h's text and lfa_coll_block, the case lists against
+   their literals (all 931 instantiations, every path), the inputs at 8 ranks,
+   and the protocol against a numpy emulation of the kernels, with and without
+   seeded faults.
 """
 import ctypes
 import json
 import os
+import re
 
 import numpy as np
 import pytest
@@ -464,3 +470,188 @@ def test_host_tree_form_cases(op):
             case.check(dt, a)
             ran += 1
     assert ran == S.n_tree_form_cases(op) == 21 * len(S.dts_of(op))
+
+
+# ------------------------------------------------------------- one-shot ----
+# tests/test_sweep_oneshot_gpu.py's cases, its layout model and its protocol
+
+SIGNAL_H = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                        "libfabric_amd", "csrc", "lfa_signal.h")
+
+
+def _define(text, name):
+    m = re.search(rf"^#define {name} +\(?([^/\n]*?)\)? *(/\*.*)?$", text, re.M)
+    assert m, name
+    return m.group(1).strip()
+
+
+def test_oneshot_layout_model():
+    """The model's constants are lfa_signal.h's (read from its text), its
+    scatter partition is lfa_coll_block's, the chunk and grid rules give the
+    shapes the cases are meant to have, and the LL interleave round-trips."""
+    from libfabric_amd import coll
+    text = open(SIGNAL_H).read()
+    assert _define(text, "LFA_SIG_MAX") == "32" and S.SIG_MAX == 32
+    assert _define(text, "LFA_SIG_AREA_BYTES") == "1u << 20" and S.SIG_AREA == 1 << 20
+    assert _define(text, "LFA_SIG_OS_OFF") == "256" and S.SIG_OS_OFF == 256
+    assert _define(text, "LFA_SIG_OS_CHUNKS") == "128" and S.SIG_OS_CHUNKS == 128
+    assert _define(text, "LFA_OS_MAX_RANKS") == "8" and S.OS_MAX_RANKS == 8
+    assert _define(text, "LFA_OS_LL_BYTES") == "16u << 10" and S.LL_BYTES == 16 << 10
+    assert _define(text, "LFA_SIG_LL_SLOT") == "2u * LFA_OS_LL_BYTES" and S.LL_SLOT == 2 * S.LL_BYTES
+    assert _define(text, "LFA_SIG_LL_PARITY") == "LFA_OS_MAX_RANKS * LFA_SIG_LL_SLOT"
+    assert S.LL_PARITY == S.OS_MAX_RANKS * S.LL_SLOT
+    assert _define(text, "LFA_SIG_LL_OFF") == "64u << 10" and S.LL_OFF == 64 << 10
+    assert _define(text, "LFA_SIG_NONE") == "0xffffffffffffffffull" and S.SIG_NONE == 2**64 - 1
+    assert coll.sig_area_bytes() == S.SIG_AREA and coll.SIG_NONE == S.SIG_NONE
+    # the areas do not overlap (the header's own #error, on the model's numbers)
+    assert S.SIG_OS_OFF + 4 * S.SIG_OS_CHUNKS * S.SIG_MAX <= S.LL_OFF
+    assert S.LL_OFF + 2 * S.LL_PARITY <= S.SIG_AREA - 64
+    for n in range(1, 9):
+        for count in (0, 1, n - 1, n, 1000, 8 * 2071 - 1):
+            soff, slen = S.os_parts(S.OS_SCATTER, n, count, 4)
+            assert [(o // 4, ln // 4) for o, ln in zip(soff, slen)] == \
+                [coll.block(count, n, r) for r in range(n)]
+    assert S.os_parts(3, 5, 10, 8) == ([0] * 5, [0, 0, 0, 80, 0])
+    assert S.os_parts(S.OS_ALL, 3, 10, 8) == ([0] * 3, [80] * 3)
+    # flagged: 4 KiB chunks up to 128 of them, then wider ones; LL: 4 KiB per workgroup
+    assert S.os_grid(S.FLAG, 1) == (4096, 1) and S.os_grid(S.FLAG, 4097) == (4096, 2)
+    assert S.os_grid(S.FLAG, 128 * 4096) == (4096, 128)
+    assert S.os_grid(S.FLAG, S.OS_BIG_PART) == (4144, 128) and S.OS_BIG_PART % 16 == 0
+    assert S.os_grid(S.LL, 1) == (None, 1) and S.os_grid(S.LL, 4097) == (None, 2)
+    assert S.os_grid(S.LL, S.LL_BYTES) == (None, 4)
+    for esz in (1, 2, 4, 8, 16):
+        for kernel in (S.FLAG, S.LL):
+            most = S.os_count(kernel, S.OS_ALL, 2, esz) * esz
+            assert most == S.OS_PART[kernel] + S.OS_ODD * esz and most <= S.LL_BYTES
+            assert S.os_grid(kernel, most)[1] == 3 and most % 4096      # the last one partial
+            assert (most % 16 != 0) == (esz < 16)                       # a tail below 16 bytes
+            for n in (3, 8):
+                soff, slen = S.os_parts(S.OS_SCATTER, n, S.os_count(kernel, S.OS_SCATTER, n, esz),
+                                        esz)
+                assert max(slen) == most and slen[-1] == most - esz
+    rng = np.random.default_rng(3)
+    for nb in (1, 15, 16, 17, 4099):
+        part = rng.integers(0, 256, nb, dtype=np.uint8)
+        data, flags = S.ll_unpack(S.ll_pack(part, 0xFFFFFFFF))
+        assert data.size == -(-nb // 16) * 16 and flags.size * 4 == data.size
+        assert np.array_equal(data[:nb], part) and not data[nb:].any()
+        assert (flags == 0xFFFFFFFF).all()
+
+
+def test_oneshot_case_lists():
+    """Every one of the 931 instantiations launch_oneshot chooses among (133
+    pairs x NLEAF 1, 2, 4, 8 flagged and 2, 4, 8 LL) is run; every pair meets
+    every path its element size has on both kernels; every op meets every
+    (path, NLEAF); the cases have the shapes their names say."""
+    seen, total = set(), 0
+    for op in OPS:
+        cases = list(S.os_cases(op, np.random.default_rng(op)))
+        assert len(cases) == S.N_OS_PAIR_CASES * len(S.dts_of(op)) + S.N_OS_OP_CASES
+        total += len(cases)
+        for kernel in (S.FLAG, S.LL):
+            mine = [c for c in cases if c.kernel == kernel]
+            for dt in S.dts_of(op):
+                assert {c.path for c in mine if c.dt == dt} == set(S.paths_of(S.esz_of(dt)))
+            assert {(c.path, c.nleaf) for c in mine if c.mode != S.OS_SCATTER} == \
+                {(p, k) for p in S.PATHS for k in S.OS_NLEAF[kernel]}, (op, kernel)
+            assert {c.mode for c in mine} == {S.OS_ALL, S.OS_SCATTER} | \
+                ({1, 3} if kernel == S.FLAG else set())
+            for nleaf in S.OS_NLEAF[kernel]:
+                assert {c.epoch for c in mine if c.nleaf == nleaf} >= set(S.OS_EPOCHS)
+            assert {c.grid for c in mine if c.done} == {1, 3}
+        for c in cases:
+            seen.add((c.op, c.dt, c.kernel, c.nleaf))
+            esz = S.esz_of(c.dt)
+            assert c.ll == S.OS_LL_ARG[c.kernel]
+            # what the launcher derives from the addresses, per path
+            if c.path == "bytes":
+                assert c.unal and not (c.vec and c.kernel == S.FLAG)
+            else:
+                assert not c.unal and c.vec == (c.path == "vec" and (
+                    c.mode != S.OS_SCATTER or all(o % 16 == 0 for o in c.soff)))
+            assert c.slot_bytes % 256 == 0 and c.slot_bytes - 256 < c.most <= c.slot_bytes
+            assert c.most % esz == 0 and (c.kernel == S.FLAG or c.most <= S.LL_BYTES)
+        assert {c.n for c in cases if c.kernel == S.FLAG} == set(range(1, 9))
+        assert any(c.chunk == 4144 and c.grid == 128 for c in cases)
+        assert any(c.kernel == S.LL and c.most == S.LL_BYTES for c in cases)
+        assert any(c.kernel == S.FLAG and c.most == S.LL_BYTES + S.esz_of(c.dt) for c in cases)
+        assert sum(1 for c in cases if c.count == 1) == 3
+        assert sum(1 for c in cases if c.mode == S.OS_SCATTER and c.want[-1] is None) == 4
+    assert total == S.N_OS_CASES == 2455
+    assert len(seen) == S.N_OS_INSTANCES == 931
+    assert seen == {(op, dt, k, nl) for op, dt in S.reduce_pairs()
+                    for k in (S.FLAG, S.LL) for nl in S.OS_NLEAF[k]}
+
+
+@pytest.mark.parametrize("op", OPS)
+def test_oneshot_inputs_stay_visible_at_8_ranks(op):
+    """S.inputs at the one-shot rows' shape and 8 ranks: replacing any one
+    input by its neighbour changes the reference on at least 0.5 % of the bulk
+    lanes, for every type of the op (the condition of
+    test_inputs_are_informative, at this sweep's own shape)."""
+    rng = np.random.default_rng(21000 + op)
+    for dt in S.dts_of(op):
+        n = S.os_count(S.FLAG, S.OS_ALL, 8, S.esz_of(dt))
+        data = S.inputs(op, dt, 8, n, rng)
+        want = S.reference(op, dt, data).reshape(n, -1)
+        for k in range(8):
+            other = list(data)
+            other[k] = data[(k + 1) % 8]
+            got = S.reference(op, dt, other).reshape(n, -1)
+            changed = (got != want).any(axis=1)[:n - S.EDGE_LANES].mean()
+            assert changed >= MIN_CHANGED, (op, dt, k, changed)
+
+
+@pytest.mark.parametrize("op", OPS)
+def test_oneshot_protocol_on_the_emulation(op):
+    """Every case of the op through os_run against OsEmu, the numpy emulation
+    of push, post, wait and reduce: the windows, the untouched check, the
+    pre-posted flags at every epoch and the final check hold together."""
+    ran = 0
+    for case in S.os_cases(op, np.random.default_rng(22000 + op)):
+        S.os_run(case, S.OsEmu())
+        ran += 1
+    assert ran == S.N_OS_PAIR_CASES * len(S.dts_of(op)) + S.N_OS_OP_CASES
+
+
+WRONG_RESULT = r" rank \d: .*differ"      # Case.check's comparison of a rank's result
+OS_FAULT_SEEN_BY = {            # fault -> (op, what os_run says)
+    "swap_node": (S.MIN, WRONG_RESULT),             # +-0 lanes: the order alone decides
+    "leaf0_for_7": (S.BAND, WRONG_RESULT),
+    "vhi_hi": (S.SUM, WRONG_RESULT),
+    "soff_rank": (S.SUM, r": slot \d at member \d differs"),
+    "post_minus_1": (S.SUM, "timed out"),
+    "no_zero_fill": (S.SUM, r": LL slot \d at member \d differs"),
+}
+
+
+@pytest.mark.parametrize("fault", S.OS_FAULTS)
+def test_oneshot_protocol_sees_seeded_faults(fault):
+    """Each fault, emulated one at a time, fails at least one case of one op
+    (float for MIN and SUM) with the message that names what went wrong."""
+    op, msg = OS_FAULT_SEEN_BY[fault]
+    dt = 8 if op in (S.MIN, S.SUM) else 5
+    failed = []
+    for case in S.os_pair_cases(op, dt, np.random.default_rng(23000)):
+        try:
+            S.os_run(case, S.OsEmu(fault))
+        except AssertionError as e:
+            assert re.search(msg, str(e)), (fault, str(e))
+            failed.append(case.what)
+    assert failed, fault
+
+
+@pytest.mark.parametrize("op", [S.MIN, S.BAND])
+@pytest.mark.parametrize("kernel", [S.FLAG, S.LL])
+def test_rotated_inputs_are_blind_to_a_leaf_read_twice(op, kernel):
+    """The gap this sweep closes, on the emulation: with three operands in
+    rotation over 8 ranks (every input there at least twice) a body that reads
+    leaf 0 in place of leaf 7 passes MIN and BAND; with S.inputs it fails."""
+    dt, rng = 5, np.random.default_rng(24000 + op)
+    n = S.os_count(kernel, S.OS_ALL, 8, 4)
+    pool = [rng.integers(0, 256, 4 * n, dtype=np.uint8) for _ in range(3)]
+    blind = S.OsCase(op, dt, 8, S.OS_ALL, n, kernel, "vec", 1, [pool[k % 3] for k in range(8)])
+    S.os_run(blind, S.OsEmu("leaf0_for_7"))
+    seeing = S.OsCase(op, dt, 8, S.OS_ALL, n, kernel, "vec", 1, S.inputs(op, dt, 8, n, rng))
+    with pytest.raises(AssertionError, match=WRONG_RESULT):
+        S.os_run(seeing, S.OsEmu("leaf0_for_7"))
