@@ -96,12 +96,16 @@ def _bind_lfa(L):
     L.lfa_host_readwritev.argtypes = [c_int, c_int, ioc_p, ioc_p, ioc_p, c_size_t]
     L.lfa_host_swapv.restype = c_int
     L.lfa_host_swapv.argtypes = [c_int, c_int, ioc_p, ioc_p, ioc_p, ioc_p, c_size_t]
-    # test-only: the write and tree entries with the vector body's form chosen as if
-    # the body were `as_bytes` bytes (the trailing argument; lfa_capi.cpp)
+    # test-only: the write, tree, fetch and compare entries with the vector body's form
+    # chosen as if the body were `as_bytes` bytes (the trailing argument; lfa_capi.cpp)
     L.lfa__write_as.restype = c_int
     L.lfa__write_as.argtypes = L.lfa_atomic_write_async.argtypes + [c_size_t]
     L.lfa__tree_as.restype = c_int
     L.lfa__tree_as.argtypes = L.lfa_reduce_tree_async.argtypes + [c_size_t]
+    L.lfa__readwrite_as.restype = c_int
+    L.lfa__readwrite_as.argtypes = L.lfa_atomic_readwrite_async.argtypes + [c_size_t]
+    L.lfa__swap_as.restype = c_int
+    L.lfa__swap_as.argtypes = L.lfa_atomic_swap_async.argtypes + [c_size_t]
 
 
 def _bind_tune(L):

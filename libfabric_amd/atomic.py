@@ -17,9 +17,10 @@ Mirrors the reference's L4 combine interface (include/ofi_atomic.h:45-90):
                                     fi_compare_atomicv)
   host_readwrite / host_swap        the fetch and compare tables on host
                                     buffers (lfa_host_readwrite / lfa_host_swap)
-  write_as / reduce_tree_as         test-only: write / reduce_tree with the
-                                    vector body's form chosen as if the body
-                                    were `as_bytes` bytes
+  write_as / reduce_tree_as / readwrite_as / swap_as
+                                    test-only: write / reduce_tree / readwrite
+                                    / swap with the vector body's form chosen
+                                    as if the body were `as_bytes` bytes
   reduce_valid / reduce_datatype_size  what write / reduce_tree / the
                                     collectives take: the table's columns plus
                                     DT.FLOAT16 and DT.BFLOAT16
@@ -184,11 +185,11 @@ def reduce_tree_put(op: int, dt: int, dsts: list[torch.Tensor], srcs: list[torch
 
 
 # ------------------------------------------------- forced forms (tests) ----
-# write / reduce_tree with the vector body's form chosen as if the body were
-# `as_bytes` bytes (lfa_split.h: lfa_form_write / lfa_form_tree); everything
-# else about the launch follows the real size.  For
-# tests/test_sweep_forms_gpu.py, which runs the forms a launcher only takes
-# from 32 or 192 MiB on small buffers; no product caller.
+# write / reduce_tree / readwrite / swap with the vector body's form chosen as
+# if the body were `as_bytes` bytes (lfa_split.h: lfa_form_write /
+# lfa_form_tree / lfa_form_fetch); everything else about the launch follows
+# the real size.  For tests/test_sweep_forms_gpu.py, which runs the forms a
+# launcher only takes from 32, 64 or 192 MiB on small buffers; no product caller.
 
 def write_as(op: int, dt: int, dst: torch.Tensor, src: torch.Tensor, cnt: int,
              as_bytes: int, stream=None) -> None:
@@ -216,6 +217,37 @@ def reduce_tree_as(op: int, dt: int, dst: torch.Tensor, srcs: list[torch.Tensor]
                             _stream_handle(stream), as_bytes)
     if rc:
         raise LfaError(rc, f"lfa__tree_as({op},{dt},{as_bytes})")
+
+
+def readwrite_as(op: int, dt: int, dst: torch.Tensor, src: torch.Tensor | None,
+                 res: torch.Tensor | None, cnt: int, as_bytes: int, stream=None) -> None:
+    """readwrite under lfa_form_fetch(as_bytes).  res may be None: the entry
+    refuses it as the public call does."""
+    _check_dev(dst, "dst")
+    esz = datatype_size(dt)
+    if any(t is not None and cnt * esz > t.nbytes for t in (dst, src, res)):
+        raise ValueError("cnt exceeds buffer size")
+    rc = lib().lfa__readwrite_as(int(op), int(dt), dst.data_ptr(),
+                                 src.data_ptr() if src is not None else None,
+                                 res.data_ptr() if res is not None else None, cnt,
+                                 _stream_handle(stream), as_bytes)
+    if rc:
+        raise LfaError(rc, f"lfa__readwrite_as({op},{dt},{as_bytes})")
+
+
+def swap_as(op: int, dt: int, dst: torch.Tensor, src: torch.Tensor, cmp: torch.Tensor,
+            res: torch.Tensor | None, cnt: int, as_bytes: int, stream=None) -> None:
+    """swap under lfa_form_fetch(as_bytes); res may be None, as above."""
+    for name, t in (("dst", dst), ("src", src), ("cmp", cmp)):
+        _check_dev(t, name)
+    esz = datatype_size(dt)
+    if any(t is not None and cnt * esz > t.nbytes for t in (dst, src, cmp, res)):
+        raise ValueError("cnt exceeds buffer size")
+    rc = lib().lfa__swap_as(int(op), int(dt), dst.data_ptr(), src.data_ptr(), cmp.data_ptr(),
+                            res.data_ptr() if res is not None else None, cnt,
+                            _stream_handle(stream), as_bytes)
+    if rc:
+        raise LfaError(rc, f"lfa__swap_as({op},{dt},{as_bytes})")
 
 
 # ------------------------------------------------------------- list forms --

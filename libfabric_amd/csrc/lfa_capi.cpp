@@ -73,7 +73,7 @@ void sync_rw_entry(void *dst, const void *src, void *res, size_t cnt) {
     note_error(-LFA_EINVAL);
     return;
   }
-  sync_finish("fetch", OP, DT, kOps[OP]->readwrite(DT, dst, src, res, cnt, nullptr));
+  sync_finish("fetch", OP, DT, kOps[OP]->readwrite(DT, dst, src, res, cnt, nullptr, 0));
 }
 
 template <int OP, int DT>
@@ -92,7 +92,7 @@ void sync_swap_entry(void *dst, const void *src, const void *cmp, void *res,
     note_error(-LFA_EINVAL);
     return;
   }
-  sync_finish("swap", OP, DT, kOps[OP]->swap(DT, dst, src, cmp, res, cnt, nullptr));
+  sync_finish("swap", OP, DT, kOps[OP]->swap(DT, dst, src, cmp, res, cnt, nullptr, 0));
 }
 
 template <int OP, int DT>
@@ -164,8 +164,9 @@ int lfa_atomic_last_error(void) {
   return rc;
 }
 
-// The write and tree launches share their validation with the lfa__write_as
-// and lfa__tree_as entries below, which differ only in passing as_bytes on.
+// The write, tree, fetch and compare launches share their validation with the
+// lfa__write_as, lfa__tree_as, lfa__readwrite_as and lfa__swap_as entries
+// below, which differ only in passing as_bytes on.
 static int write_as(enum lfa_op op, enum lfa_datatype dt, void *dst, const void *src,
                     size_t cnt, void *stream, size_t as_bytes) {
   if ((unsigned)op >= LFA_WRITE_OP_CNT || !reducible(op, dt))
@@ -190,25 +191,35 @@ int lfa_atomic_write_async(enum lfa_op op, enum lfa_datatype dt, void *dst,
   return write_as(op, dt, dst, src, cnt, stream, 0);
 }
 
-int lfa_atomic_readwrite_async(enum lfa_op op, enum lfa_datatype dt, void *dst,
-                               const void *src, void *res, size_t cnt,
-                               void *stream) {
+static int readwrite_as(enum lfa_op op, enum lfa_datatype dt, void *dst, const void *src,
+                        void *res, size_t cnt, void *stream, size_t as_bytes) {
   if ((unsigned)op >= LFA_READWRITE_OP_CNT || (unsigned)dt >= LFA_DATATYPE_CNT ||
       !in_rw_table(op, dt))
     return -LFA_EOPNOTSUPP;
   if (cnt && (!dst || !res || (op != LFA_ATOMIC_READ && !src)))
     return -LFA_EINVAL;
-  return kOps[op]->readwrite(dt, dst, src, res, cnt, stream);
+  return kOps[op]->readwrite(dt, dst, src, res, cnt, stream, as_bytes);
+}
+
+static int swap_as(enum lfa_op op, enum lfa_datatype dt, void *dst, const void *src,
+                   const void *cmp, void *res, size_t cnt, void *stream, size_t as_bytes) {
+  if (op < LFA_CSWAP || op > LFA_MSWAP || (unsigned)dt >= LFA_DATATYPE_CNT ||
+      !in_swap_table(op, dt))
+    return -LFA_EOPNOTSUPP;
+  if (cnt && (!dst || !src || !cmp || !res)) return -LFA_EINVAL;
+  return kOps[op]->swap(dt, dst, src, cmp, res, cnt, stream, as_bytes);
+}
+
+int lfa_atomic_readwrite_async(enum lfa_op op, enum lfa_datatype dt, void *dst,
+                               const void *src, void *res, size_t cnt,
+                               void *stream) {
+  return readwrite_as(op, dt, dst, src, res, cnt, stream, 0);
 }
 
 int lfa_atomic_swap_async(enum lfa_op op, enum lfa_datatype dt, void *dst,
                           const void *src, const void *cmp, void *res,
                           size_t cnt, void *stream) {
-  if (op < LFA_CSWAP || op > LFA_MSWAP || (unsigned)dt >= LFA_DATATYPE_CNT ||
-      !in_swap_table(op, dt))
-    return -LFA_EOPNOTSUPP;
-  if (cnt && (!dst || !src || !cmp || !res)) return -LFA_EINVAL;
-  return kOps[op]->swap(dt, dst, src, cmp, res, cnt, stream);
+  return swap_as(op, dt, dst, src, cmp, res, cnt, stream, 0);
 }
 
 int lfa_reduce_tree_async(enum lfa_op op, enum lfa_datatype dt, void *dst,
@@ -227,11 +238,11 @@ int lfa_reduce_tree_async(enum lfa_op op, enum lfa_datatype dt, void *dst,
 }
 
 // Test-only entries (internal, as lfa__tune_* in liblfa_tune.so; not in
-// include/lfa_atomic.h): the write and tree calls above with the vector
-// body's form chosen as if the body were `as_bytes` bytes (lfa_split.h; 0: by
-// the real size), so that tests/test_sweep_forms_gpu.py runs every form those
-// launchers only take from 32 or 192 MiB on a 40 KiB buffer.  The tree entry
-// goes to the tree launcher whatever nsrc is.
+// include/lfa_atomic.h): the write, tree, fetch and compare calls above with
+// the vector body's form chosen as if the body were `as_bytes` bytes
+// (lfa_split.h; 0: by the real size), so that tests/test_sweep_forms_gpu.py
+// runs every form those launchers only take from 32, 64 or 192 MiB on a 40 or
+// 50 KiB buffer.  The tree entry goes to the tree launcher whatever nsrc is.
 int lfa__write_as(int op, int dt, void *dst, const void *src, size_t cnt, void *stream,
                   size_t as_bytes) {
   return write_as((lfa_op)op, (lfa_datatype)dt, dst, src, cnt, stream, as_bytes);
@@ -241,6 +252,16 @@ int lfa__tree_as(int op, int dt, void *dst, const void *const *srcs, int nsrc, s
                  void *stream, size_t as_bytes) {
   if (int rc = tree_check((lfa_op)op, (lfa_datatype)dt, dst, srcs, nsrc, cnt)) return rc;
   return kOps[op]->tree(dt, dst, srcs, nsrc, cnt, stream, as_bytes);
+}
+
+int lfa__readwrite_as(int op, int dt, void *dst, const void *src, void *res, size_t cnt,
+                      void *stream, size_t as_bytes) {
+  return readwrite_as((lfa_op)op, (lfa_datatype)dt, dst, src, res, cnt, stream, as_bytes);
+}
+
+int lfa__swap_as(int op, int dt, void *dst, const void *src, const void *cmp, void *res,
+                 size_t cnt, void *stream, size_t as_bytes) {
+  return swap_as((lfa_op)op, (lfa_datatype)dt, dst, src, cmp, res, cnt, stream, as_bytes);
 }
 
 int lfa_reduce_tree_put_async(enum lfa_op op, enum lfa_datatype dt,

@@ -217,11 +217,11 @@ constexpr lfa_launch_treeput_t op_treeput = nullptr;
 
 #if LFA_OP <= 11
 static int op_readwrite(int dt, void *dst, const void *src, void *res, size_t cnt,
-                        void *stream) {
+                        void *stream, size_t as_bytes) {
   return lfa::by_type<LFA_OP>(dt, [&](auto *tag) {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     return lfa::launch_readwrite<LFA_OP, T>(dst, src, res, cnt,
-                                            (hipStream_t)stream);
+                                            (hipStream_t)stream, as_bytes);
   });
 }
 static int op_readwritev(int dt, const lfa_iov_args *a, unsigned ntile, void *stream) {
@@ -236,11 +236,11 @@ constexpr lfa_launch_fetchv_t op_swapv = nullptr;
 constexpr lfa_launch_readwrite_t op_readwrite = nullptr;
 constexpr lfa_launch_fetchv_t op_readwritev = nullptr;
 static int op_swap(int dt, void *dst, const void *src, const void *cmp, void *res,
-                   size_t cnt, void *stream) {
+                   size_t cnt, void *stream, size_t as_bytes) {
   return lfa::by_type<LFA_OP>(dt, [&](auto *tag) {
     typedef typename std::remove_pointer<decltype(tag)>::type T;
     return lfa::launch_swap<LFA_OP, T>(dst, src, cmp, res, cnt,
-                                       (hipStream_t)stream);
+                                       (hipStream_t)stream, as_bytes);
   });
 }
 

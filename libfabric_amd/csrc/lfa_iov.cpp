@@ -217,7 +217,7 @@ int lfa_atomic_readwritev_async(enum lfa_op op, enum lfa_datatype dt,
   // the tapered and nt-drained bodies by size, which a 256 MiB segment keeps.
   if (t.nseg() == 1)
     return kOps[op]->readwrite(dt, dst[only].addr, has_src ? src[only].addr : nullptr,
-                               res[only].addr, dst[only].count, stream);
+                               res[only].addr, dst[only].count, stream, 0);
   return iov_launch(t, stream, [&](const lfa_iov_args *a, unsigned ntile) {
     return kOps[op]->readwritev(dt, a, ntile, stream);
   });
@@ -248,7 +248,7 @@ int lfa_atomic_swapv_async(enum lfa_op op, enum lfa_datatype dt, const struct lf
   if (!t.nseg()) return 0;
   if (t.nseg() == 1)
     return kOps[op]->swap(dt, dst[only].addr, src[only].addr, cmp[only].addr, res[only].addr,
-                          dst[only].count, stream);
+                          dst[only].count, stream, 0);
   return iov_launch(t, stream, [&](const lfa_iov_args *a, unsigned ntile) {
     return kOps[op]->swapv(dt, a, ntile, stream);
   });

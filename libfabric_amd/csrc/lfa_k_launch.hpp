@@ -13,12 +13,12 @@ namespace lfa {
 // each operand per wave, nt loads and stores.
 constexpr int kUnroll = 4;
 
-// Which form of the body launch_write and launch_tree_body take by its size
-// is lfa_split.h's lfa_form_write / lfa_form_tree (thresholds there): plain C,
-// checked on the host by tools/split_host_check.cpp.  Those two launchers'
-// last argument, as_bytes, is theirs: 0 in the product, a pretended body size
-// from the lfa__write_as and lfa__tree_as test entries (lfa_capi.cpp).
-// launch_fetch decides inline.
+// Which form of the body launch_write, launch_tree_body and launch_fetch take
+// by its size is lfa_split.h's lfa_form_write / lfa_form_tree / lfa_form_fetch
+// (thresholds there): plain C, checked on the host by
+// tools/split_host_check.cpp.  Those launchers' as_bytes argument is theirs: 0
+// in the product, a pretended body size from the lfa__write_as, lfa__tree_as,
+// lfa__readwrite_as and lfa__swap_as test entries (lfa_capi.cpp).
 
 // combine_lds_taper from LFA_TAPER_BYTES per operand (up to kSc1Bytes; the
 // nt-store path above keeps the uniform grid), the last 1/kTaperDiv tapered
@@ -541,7 +541,7 @@ static int launch_oneshot(const lfa_oneshot &h, hipStream_t s, int ll = -1) {
 // is co-aligned mod 16, element path for heads, tails and the rest.
 template <typename T, typename MakeF>
 static int launch_fetch(const void *const *ptrs, int nptr, size_t cnt,
-                        hipStream_t s, MakeF &&make) {
+                        hipStream_t s, size_t as_bytes, MakeF &&make) {
   constexpr size_t E = sizeof(T);
   if (cnt == 0) return 0;
   const lfa_path path = lfa_split_path(ptrs, nptr, nullptr, 0, E);
@@ -581,28 +581,34 @@ static int launch_fetch(const void *const *ptrs, int nptr, size_t cnt,
     // three interleaved runs of 20 rounds on one box; UT 1 / 2 with the last
     // 1/16 .. 1/2 tapered measured within that (profiles/r06_tune_fetch_taper_*.jsonl).
     // Below kSc1Bytes the two-input readwrite takes the same tail from
-    // kFetchTaperBytes, on its write-through drained body (tune variant 21 vs
+    // LFA_FETCH_TAPER_BYTES, on its write-through drained body (tune variant 21 vs
     // 6: 64 MiB 39.1 / 38.6 -> 38.5 / 38.4 us, 128 MiB 83.0 -> 81.7 us); the
     // compare body keeps its undrained form there, which the tapered one
     // trailed at 64 MiB (48.5 vs 49.5-50.1 us) and tied at 128
     // (profiles/r06_tune_fetch_taper_sc1.jsonl).
+    // The choice itself is lfa_form_fetch (lfa_split.h).
     constexpr int U = 4;
     constexpr bool D = FF::kIn == 2;
-    constexpr size_t kFetchTaperBytes = (size_t)64 << 20;
     constexpr size_t hv = (size_t)kLdsWaves * 64 * U, tv = (size_t)kLdsWaves * 64;
-    const bool nt = nvec * 16 >= kSc1Bytes;
-    if (nt || (FF::kIn == 2 && nvec * 16 >= kFetchTaperBytes)) {
-      const lfa_taper tp = lfa_split_taper(nvec, 4, hv, tv);
-      const dim3 grid(tp.nhead + tp.ntail);
-      if (nt)
-        hipLaunchKernelGGL((fetch_lds_taper<U, 1, kStoreNt, FF>), grid, dim3(kLdsWaves * 64), 0,
-                           s, f, nvec, tp.split, tp.nhead);
-      else
-        hipLaunchKernelGGL((fetch_lds_taper<U, 1, kStoreSc1, FF>), grid, dim3(kLdsWaves * 64),
-                           0, s, f, nvec, tp.split, tp.nhead);
-    } else {
-      hipLaunchKernelGGL((fetch_lds<U, kStoreSc1, FF, D>), dim3(grid_for(nvec, hv, 0x7fffffffu)),
-                         dim3(kLdsWaves * 64), 0, s, f, nvec);
+    const lfa_fetch_form form = lfa_form_fetch(lfa_form_bytes(nvec, as_bytes), FF::kIn);
+    switch (form) {
+      case LFA_FETCH_TAPER_NT:
+      case LFA_FETCH_TAPER_SC1: {
+        // the last quarter of the vectors in 1-KiB tiles
+        const lfa_taper tp = lfa_split_taper(nvec, 4, hv, tv);
+        const dim3 grid(tp.nhead + tp.ntail);
+        if (form == LFA_FETCH_TAPER_NT)
+          hipLaunchKernelGGL((fetch_lds_taper<U, 1, kStoreNt, FF>), grid, dim3(kLdsWaves * 64), 0,
+                             s, f, nvec, tp.split, tp.nhead);
+        else
+          hipLaunchKernelGGL((fetch_lds_taper<U, 1, kStoreSc1, FF>), grid, dim3(kLdsWaves * 64),
+                             0, s, f, nvec, tp.split, tp.nhead);
+        break;
+      }
+      case LFA_FETCH_LDS:
+        hipLaunchKernelGGL((fetch_lds<U, kStoreSc1, FF, D>), dim3(grid_for(nvec, hv, 0x7fffffffu)),
+                           dim3(kLdsWaves * 64), 0, s, f, nvec);
+        break;
     }
   }
   if (sp.head + sp.tail)
@@ -613,12 +619,12 @@ static int launch_fetch(const void *const *ptrs, int nptr, size_t cnt,
 
 template <int OP, typename T>
 static int launch_readwrite(void *dst, const void *src, void *res, size_t cnt,
-                            hipStream_t s) {
+                            hipStream_t s, size_t as_bytes = 0) {
   if constexpr (!rw_supported<OP, T>()) {
     return -LFA_EOPNOTSUPP;
   } else {
     const void *ptrs[3] = {dst, res, OP == OP_READ ? dst : src};
-    return launch_fetch<T>(ptrs, 3, cnt, s, [&](auto aligned, size_t head) {
+    return launch_fetch<T>(ptrs, 3, cnt, s, as_bytes, [&](auto aligned, size_t head) {
       constexpr bool A = decltype(aligned)::value;
       const size_t hb = head * sizeof(T);
       return RwF<OP, T, A>{(char *)dst, (const char *)src, (char *)res,
@@ -631,12 +637,12 @@ static int launch_readwrite(void *dst, const void *src, void *res, size_t cnt,
 
 template <int OP, typename T>
 static int launch_swap(void *dst, const void *src, const void *cmp, void *res,
-                       size_t cnt, hipStream_t s) {
+                       size_t cnt, hipStream_t s, size_t as_bytes = 0) {
   if constexpr (!swap_supported<OP, T>()) {
     return -LFA_EOPNOTSUPP;
   } else {
     const void *ptrs[4] = {dst, src, cmp, res};
-    return launch_fetch<T>(ptrs, 4, cnt, s, [&](auto aligned, size_t head) {
+    return launch_fetch<T>(ptrs, 4, cnt, s, as_bytes, [&](auto aligned, size_t head) {
       constexpr bool A = decltype(aligned)::value;
       const size_t hb = head * sizeof(T);
       return SwapF<OP, T, A>{(char *)dst, (const char *)src, (const char *)cmp,

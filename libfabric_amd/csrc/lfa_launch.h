@@ -6,10 +6,10 @@
  * entries; a form the op does not have is NULL.  Both sides take the
  * signatures from here.  Every entry returns 0 or a negative LFA_E* code;
  * `dt` is an enum lfa_datatype (write: | LFA_WRITE_MAPPED, lfa_signal.h),
- * `stream` a hipStream_t.  write and tree end in `as_bytes`: 0 from every
- * product caller; otherwise the vector body's form is chosen as if the body
- * were that many bytes (lfa_split.h; the lfa__write_as / lfa__tree_as test
- * entries).  oneshot ends in `ll`: -1 from every product caller (the
+ * `stream` a hipStream_t.  write, tree, readwrite and swap end in `as_bytes`:
+ * 0 from every product caller; otherwise the vector body's form is chosen as
+ * if the body were that many bytes (lfa_split.h; the lfa__write_as /
+ * lfa__tree_as / lfa__readwrite_as / lfa__swap_as test entries).  oneshot ends in `ll`: -1 from every product caller (the
  * launcher's own choice of kernel); 0 the flagged kernel, 1 the LL kernel (the
  * lfa__oneshot_as test entry).
  */
@@ -35,9 +35,9 @@ typedef int (*lfa_launch_treeput_t)(int dt, void *const *dsts, int ndst, const v
                                     int nsrc, size_t cnt, void *stream);
 typedef int (*lfa_launch_oneshot_t)(int dt, const struct lfa_oneshot *a, void *stream, int ll);
 typedef int (*lfa_launch_readwrite_t)(int dt, void *dst, const void *src, void *res, size_t cnt,
-                                      void *stream);
+                                      void *stream, size_t as_bytes);
 typedef int (*lfa_launch_swap_t)(int dt, void *dst, const void *src, const void *cmp, void *res,
-                                 size_t cnt, void *stream);
+                                 size_t cnt, void *stream, size_t as_bytes);
 
 struct lfa_op_launch {
   lfa_launch_write_t write;         /* ops 0..9, 11 */

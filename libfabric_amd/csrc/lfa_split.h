@@ -1,7 +1,7 @@
 /* lfa_split.h — how one buffer of a call is cut up, in one place: the path its
  * operands' addresses permit, the head / vector body / tail of the vector
  * path, the tapered grid of a vector body, and the form of that body a
- * launcher picks by size (lfa_form_write, lfa_form_tree).  Shared by every launcher
+ * launcher picks by size (lfa_form_write, lfa_form_tree, lfa_form_fetch).  Shared by every launcher
  * (lfa_k_launch.hpp), the list kernels and their host side (lfa_iov.h) and
  * the tuning library.  Plain C: no HIP types.
  */
@@ -82,7 +82,7 @@ LFA_SPLIT_FN struct lfa_taper lfa_split_taper(size_t nvec, size_t div, size_t hv
   return t;
 }
 
-/* Which form of a vector body launch_write and launch_tree_body run, by the body's size in bytes
+/* Which form of a vector body launch_write, launch_tree_body and launch_fetch run, by the body's size in bytes
  * per operand (nvec * 16).  The launchers (lfa_k_launch.hpp) switch on these
  * and on nothing else; the measurements behind every threshold are quoted
  * there.  Pure functions of their arguments: tools/split_host_check.cpp
@@ -93,8 +93,9 @@ LFA_SPLIT_FN struct lfa_taper lfa_split_taper(size_t nvec, size_t div, size_t hv
 /* A launcher's `as_bytes` argument: 0 chooses by the real body, anything
  * else as if the body were that many bytes.  Only the form follows it; the
  * split, the grid and the kernel arguments come from the real size.  The
- * product passes 0; the lfa__write_as / lfa__tree_as entries (lfa_capi.cpp)
- * let the tests run every large-size form on a small buffer. */
+ * product passes 0; the lfa__write_as / lfa__tree_as / lfa__readwrite_as /
+ * lfa__swap_as entries (lfa_capi.cpp) let the tests run every large-size
+ * form on a small buffer. */
 LFA_SPLIT_FN size_t lfa_form_bytes(size_t nvec, size_t as_bytes) {
   return as_bytes ? as_bytes : nvec * 16;
 }
@@ -143,6 +144,27 @@ LFA_SPLIT_FN struct lfa_tree_form lfa_form_tree(size_t body_bytes, int nsrc, int
     f.cap_lds = nsrc >= 3 && nsrc <= 8;
   }
   return f;
+}
+
+/* The fetch and compare tables' vector body (launch_fetch), by the body's
+ * size per operand and the functor's inputs (nin: 1 ATOMIC_READ, 2 the other
+ * readwrite ops, 3 the compare table):
+ *
+ *   below LFA_FETCH_TAPER_BYTES   fetch_lds, write-through, drained iff nin == 2
+ *   from LFA_FETCH_TAPER_BYTES    nin == 2 only: fetch_lds_taper, write-through
+ *   from LFA_SC1_BYTES            every nin: fetch_lds_taper, nt stores
+ */
+#define LFA_FETCH_TAPER_BYTES ((size_t)64 << 20) /* two-input fetch: tapered tail from here */
+
+enum lfa_fetch_form {
+  LFA_FETCH_LDS,       /* fetch_lds, write-through stores */
+  LFA_FETCH_TAPER_SC1, /* fetch_lds_taper, write-through stores */
+  LFA_FETCH_TAPER_NT   /* fetch_lds_taper, nt stores */
+};
+
+LFA_SPLIT_FN enum lfa_fetch_form lfa_form_fetch(size_t body_bytes, int nin) {
+  if (body_bytes >= LFA_SC1_BYTES) return LFA_FETCH_TAPER_NT;
+  return nin == 2 && body_bytes >= LFA_FETCH_TAPER_BYTES ? LFA_FETCH_TAPER_SC1 : LFA_FETCH_LDS;
 }
 
 #endif /* LFA_SPLIT_H */

@@ -4,7 +4,7 @@ tests/test_sweep_gpu.py runs every (op, datatype) pair through every tree,
 tree-put and list-form kernel instantiation liblfa.so holds,
 tests/test_sweep_tables_gpu.py every entry of the write, fetch and compare
 tables through its own kernels, tests/test_sweep_forms_gpu.py every form the
-write and tree launchers only take at large sizes, tests/test_sweep_oneshot_gpu.py
+write, tree and fetch launchers only take at large sizes, tests/test_sweep_oneshot_gpu.py
 every one-shot kernel, one rank at a time (the last parts of this module);
 tests/test_sweep_cpu.py runs the same cases through the host forms and
 checks the conditions below on the inputs themselves.  This module builds the
@@ -693,11 +693,11 @@ class TableCase:
             assert_same(dt, self.view(got, "dst").copy(), self.want, f"{self.what} dst")
 
 
-def carve_table(dt, names, data, want, exact, path, k=0, what=""):
+def carve_table(dt, names, data, want, exact, path, k=0, what="", count=lanes):
     """A TableCase for the operands `data` (name -> bytes; res, which has
-    none, holds OUT_FILL) in `names` order on `path`."""
+    none, holds OUT_FILL) in `names` order on `path`; count(esz) elements."""
     esz = esz_of(dt)
-    n = lanes(esz)
+    n = count(esz)
     assert n * esz == data["dst"].size
     offs, odd = table_layout(esz, path, names, k)
     segs, size = L.plan([n] * len(names), offs, esz)
@@ -708,10 +708,10 @@ def carve_table(dt, names, data, want, exact, path, k=0, what=""):
                      f"{what} {path}" + (f" odd={odd}" if odd else ""), segs, path, odd)
 
 
-def _on_paths(dt, names, data, want, exact, paths, turn, what):
+def _on_paths(dt, names, data, want, exact, paths, turn, what, count=lanes):
     for path in paths_of(esz_of(dt)):
         if path in paths:
-            yield carve_table(dt, names, data, want, exact, path, turn[path], what)
+            yield carve_table(dt, names, data, want, exact, path, turn[path], what, count)
             turn[path] += 1
 
 
@@ -726,12 +726,13 @@ def write_cases(op, dts, rng, paths=PATHS):
             False, paths, turn, f"write op={op} dt={dt}"))
 
 
-def readwrite_cases(op, dts, rng, paths=PATHS):
+def readwrite_cases(op, dts, rng, paths=PATHS, count=lanes):
     """Every case of lfa_atomic_readwrite_async for one op.  ATOMIC_READ has
-    no src: dst must come back as it was, byte for byte."""
+    no src: dst must come back as it was, byte for byte.  count(esz): the
+    elements per operand."""
     turn = dict.fromkeys(PATHS, 0)
     for dt in dts:
-        n = lanes(esz_of(dt))
+        n = count(esz_of(dt))
         if op == READ:
             (d,) = inputs(SUM, dt, 1, n, rng)
             names, data = TABLE_OPERANDS["read"], {"dst": d}
@@ -741,17 +742,19 @@ def readwrite_cases(op, dts, rng, paths=PATHS):
             names, data = TABLE_OPERANDS["readwrite"], {"dst": d, "src": s}
             want = reference_readwrite(op, dt, d, s)
         yield from ((dt, c) for c in _on_paths(dt, names, data, want, op == READ, paths, turn,
-                                               f"readwrite op={op} dt={dt}"))
+                                               f"readwrite op={op} dt={dt}", count))
 
 
-def swap_cases(op, dts, rng, paths=PATHS):
-    """Every case of lfa_atomic_swap_async for one op."""
+def swap_cases(op, dts, rng, paths=PATHS, count=lanes):
+    """Every case of lfa_atomic_swap_async for one op; count(esz): the
+    elements per operand."""
     turn = dict.fromkeys(PATHS, 0)
     for dt in dts:
-        d, s, c = swap_inputs(op, dt, lanes(esz_of(dt)), rng)
+        d, s, c = swap_inputs(op, dt, count(esz_of(dt)), rng)
         yield from ((dt, case) for case in _on_paths(
             dt, TABLE_OPERANDS["swap"], {"dst": d, "src": s, "cmp": c},
-            reference_swap(op, dt, d, s, c), True, paths, turn, f"swap op={op} dt={dt}"))
+            reference_swap(op, dt, d, s, c), True, paths, turn, f"swap op={op} dt={dt}",
+            count))
 
 
 def operands_of(table: str, op: int):
@@ -845,6 +848,74 @@ def tree_form_cases(op, dt, rng):
 
 def n_tree_form_cases(op) -> int:
     return len(dts_of(op)) * len(TREE_NSRC) * (1 + len(TREE_ALIAS))
+
+
+# The forms launch_fetch only takes from 64 or 192 MiB per operand
+# (lfa_split.h: lfa_form_fetch), through the lfa__readwrite_as and lfa__swap_as
+# entries.  nin: the functor's inputs: 1 ATOMIC_READ (dst), 2 the other
+# readwrite ops (dst, src), 3 the compare table (dst, src, cmp).
+
+FETCH_FORMS = ("fetch_lds sc1", "fetch_lds_taper sc1", "fetch_lds_taper nt")     # enum order
+FETCH_AS = (("fetch_lds_taper nt", 192 * MIB), ("fetch_lds_taper sc1", 64 * MIB))
+# the form cases of the two tables: (pairs on the vec path + on the head
+# path) per forced form; 24 of the 145 readwrite pairs are 16-byte types (2 of
+# them ATOMIC_READ's, which has no tapered write-through form), 14 of the 84
+# compare pairs
+N_RW_FORM_CASES = (145 + 121) + (132 + 110)
+N_SWAP_FORM_CASES = 84 + 70
+
+
+def model_fetch_form(nbytes: int, nin: int) -> str:
+    """launch_fetch: below 64 MiB fetch_lds with write-through stores; from
+    64 MiB the tapered kernel with write-through stores for two-input
+    functors only; from 192 MiB the tapered kernel with nt stores for all."""
+    if nbytes >= 192 * MIB:
+        return "fetch_lds_taper nt"
+    return "fetch_lds_taper sc1" if nin == 2 and nbytes >= 64 * MIB else "fetch_lds sc1"
+
+
+def fetch_nin(table: str, op: int) -> int:
+    return 3 if table == "swap" else 1 if op == READ else 2
+
+
+def fetch_lanes(esz: int) -> int:
+    """The count of the fetch form cases.  launch_fetch tapers the last 1/4 in
+    256-vector workgroups behind 1024-vector head workgroups, where lanes()
+    leaves ONE head workgroup; this gives 3172..3174 vectors: two whole head
+    workgroups, four whole tail workgroups, a last one of 100..102 vectors
+    (a whole wave and a partial one) and, below 16 bytes, an element tail.
+    One element past a whole number of vectors, not lanes()'s three: behind
+    the head path's 16 / esz - 1 head elements three more leave no tail at 4
+    bytes, one leaves two elements at 1, 2 and 4 bytes.  (At 8 bytes no count
+    has a tail on both paths: the one head element takes it.)"""
+    return (48 * 1024 + 16 * 101) // esz + 1
+
+
+def readwrite_form_cases(op, dts, rng):
+    """(form, as_bytes, dt, TableCase): every type of the op on the vec and
+    head paths under the tapered nt-store fetch body and, except ATOMIC_READ
+    (one input: the launcher never gives it that form), under the tapered
+    write-through one."""
+    for form, as_bytes in FETCH_AS:
+        if model_fetch_form(as_bytes, fetch_nin("readwrite", op)) != form:
+            assert op == READ and form == "fetch_lds_taper sc1"
+            continue
+        for dt, case in readwrite_cases(op, dts, rng, FORM_PATHS, fetch_lanes):
+            yield form, as_bytes, dt, case
+
+
+def swap_form_cases(op, dts, rng):
+    """(form, as_bytes, dt, TableCase): every type of the op on the vec and
+    head paths under the tapered nt-store compare body."""
+    form, as_bytes = FETCH_AS[0]
+    assert model_fetch_form(as_bytes, fetch_nin("swap", op)) == form
+    for dt, case in swap_cases(op, dts, rng, FORM_PATHS, fetch_lanes):
+        yield form, as_bytes, dt, case
+
+
+def n_fetch_form_cases(table: str, op: int, dts) -> int:
+    forms = sum(model_fetch_form(a, fetch_nin(table, op)) == f for f, a in FETCH_AS)
+    return (forms if table == "readwrite" else 1) * n_table_cases(dts, FORM_PATHS)
 
 
 # ------------------------------------------------------------- one-shot ----

@@ -2,7 +2,7 @@
 against the header, prints the path and the head / nvec / body / tail split of
 a grid of buffers and the taper split around its tile boundaries; the same
 quantities are computed here from tests/_iov_layout.py's classification.  It
-also prints the form launch_write and launch_tree_body pick by size (lfa_form_*), with and without
+also prints the form launch_write, launch_tree_body and launch_fetch pick by size (lfa_form_*), with and without
 an as_bytes override, which is held to tests/_sweep.py's model of the
 launchers' table.  The program is built once more with ASan + UBSan and run
 stand-alone."""
@@ -99,7 +99,9 @@ def test_forms_match_model(lines):
     mapped and not, the tree at every fan-in 2..32
     and element size.  Every form appears, and without as_bytes nothing but
     the small forms below 32 MiB."""
-    rows = [ln[1:] for ln in lines if ln[0] == "form"]
+    # the `form fetch` rows are test_fetch_forms_match_model's
+    rows = [ln[1:] for ln in lines if ln[0] == "form" and ln[1] != "fetch"]
+    assert {ln[1] for ln in lines if ln[0] == "form"} == {"write", "tree", "fetch"}
     seen, keys = set(), set()
     for kind, *rest in rows:
         as_bytes, real, *args = (int(x) for x in rest)
@@ -127,6 +129,36 @@ def test_forms_match_model(lines):
             assert {("tree", forced, nbytes, nsrc, S.leaves_of(nsrc), esz)
                     for nsrc in range(2, 33) for esz in (1, 2, 4, 8, 16)} <= keys
     assert len(rows) == 2 * len(FORM_SIZES) * (2 + 31 * 5)
+
+
+def test_fetch_forms_match_model(lines):
+    """lfa_form_fetch against tests/_sweep.py's model_fetch_form, which is
+    written from launch_fetch's table of forms and calls no C: over the same
+    sizes, real and forced, for 1 (ATOMIC_READ), 2 (the other readwrite ops)
+    and 3 (the compare table) inputs.  Every form appears; without as_bytes
+    nothing but fetch_lds below 64 MiB; at 64 MiB itself only two-input
+    functors leave it."""
+    rows = [[int(x) for x in ln[2:]] for ln in lines if ln[:2] == ["form", "fetch"]]
+    seen, keys = set(), set()
+    for as_bytes, real, nin, got in rows:
+        case = (as_bytes, real, nin, got)
+        assert real == SMALL if as_bytes else real in FORM_SIZES, case
+        nbytes = as_bytes or real
+        form = S.model_fetch_form(nbytes, nin)
+        assert S.FETCH_FORMS[got] == form, case
+        if not as_bytes and real < 64 * S.MIB:
+            assert form == "fetch_lds sc1", case
+        if nbytes == 64 * S.MIB:
+            assert (form == "fetch_lds sc1") == (nin != 2), case
+        seen.add(form)
+        keys.add((bool(as_bytes), nbytes, nin))
+    assert seen == set(S.FETCH_FORMS) and len(S.FETCH_FORMS) == 3
+    assert keys == {(forced, nbytes, nin) for forced in (False, True) for nbytes in FORM_SIZES
+                    for nin in (1, 2, 3)}
+    assert len(FORM_SIZES) == 11 and len(rows) == 66      # 2 x 11 sizes x 3 functor shapes
+    # the forced sizes of the form sweep are the thresholds themselves
+    for form, as_bytes in S.FETCH_AS:
+        assert S.model_fetch_form(as_bytes, 2) == form != S.model_fetch_form(as_bytes - 16, 2)
 
 
 def test_split_check_under_sanitizers(tmp_path, lines):

@@ -19,7 +19,11 @@
 4. The forced large-size forms (tests/test_sweep_forms_gpu.py): the case
    counts, the form tests/_sweep.py's model names for each as_bytes, the tile
    shapes lanes() gives the tapered grids and the tree bodies, and the case
-   list through the host forms.
+   list through the host forms.  For launch_fetch's forms, which taper a
+   quarter: a count of their own (fetch_lanes), held to two whole head
+   workgroups, two whole tail workgroups and a partial one with a whole and a
+   partial wave; the thresholds and tile sizes held to the source text; and
+   every readwrite and compare case through lfa_host_readwrite / lfa_host_swap.
 5. The one-shot sweep (tests/test_sweep_oneshot_gpu.py): the layout model
    against lfa_signal.h's text and lfa_coll_block, the case lists against
    their literals (all 931 instantiations, every path), the inputs at 8 ranks,
@@ -470,6 +474,144 @@ def test_host_tree_form_cases(op):
             case.check(dt, a)
             ran += 1
     assert ran == S.n_tree_form_cases(op) == 21 * len(S.dts_of(op))
+
+
+# launch_fetch's forms (tests/test_sweep_forms_gpu.py): nt for every pair,
+# tapered write-through for the two-input readwrite pairs (all but ATOMIC_READ)
+N_RW_FORM_CASES = (145 + 121) + (132 + 110)     # 24 sixteen-byte pairs, 2 of them ATOMIC_READ's
+N_SWAP_FORM_CASES = 84 + 70
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                    "libfabric_amd", "csrc")
+
+
+def test_fetch_form_constants_are_the_sources():
+    """The thresholds and the taper's tile sizes the model and fetch_lanes
+    assume are launch_fetch's, read from the source text: 64 and 192 MiB in
+    lfa_split.h; 4 waves x 64 lanes x U = 4 vectors per head workgroup, 4 x 64
+    per tail workgroup, the last 1/4 tapered, in lfa_k_launch.hpp."""
+    split = open(os.path.join(CSRC, "lfa_split.h")).read()
+    assert _define(split, "LFA_FETCH_TAPER_BYTES") == "(size_t)64 << 20"
+    assert _define(split, "LFA_SC1_BYTES") == "(size_t)192 << 20"
+    assert dict(S.FETCH_AS) == {"fetch_lds_taper sc1": 64 << 20, "fetch_lds_taper nt": 192 << 20}
+    assert re.search(r"enum lfa_fetch_form \{\s*LFA_FETCH_LDS,[^}]*LFA_FETCH_TAPER_SC1,[^}]*"
+                     r"LFA_FETCH_TAPER_NT\b", split)           # FETCH_FORMS' order
+    kern = open(os.path.join(CSRC, "lfa_kernels.hpp")).read()
+    assert re.search(r"^constexpr int kLdsWaves = 4;", kern, re.M)
+    launch = open(os.path.join(CSRC, "lfa_k_launch.hpp")).read()
+    body = launch[launch.index("static int launch_fetch("):launch.index("static int launch_readwrite(")]
+    assert "kFetchTaperBytes" not in launch
+    assert re.search(r"constexpr int U = 4;", body)
+    assert re.search(r"constexpr size_t hv = \(size_t\)kLdsWaves \* 64 \* U, "
+                     r"tv = \(size_t\)kLdsWaves \* 64;", body)
+    assert re.findall(r"lfa_split_taper\(([^)]*)\)", body) == ["nvec, 4, hv, tv"]
+    assert re.findall(r"switch \(([^\n]*)\) \{", body) == ["form"]
+    assert "form = lfa_form_fetch(lfa_form_bytes(nvec, as_bytes), FF::kIn);" in body
+    assert re.findall(r"fetch_lds_taper<([^>]*)>", body) == ["U, 1, kStoreNt, FF", "U, 1, kStoreSc1, FF"]
+    hv, tv, div = 4 * 64 * 4, 4 * 64, 4
+    assert (hv, tv, div) == (1024, 256, 4) == S.model_taper.__defaults__ + (4,)
+
+
+def test_fetch_form_shapes():
+    """fetch_lanes() under launch_fetch's taper (the last 1/4 in 256-vector
+    workgroups behind 1024-vector ones), at every element size on the vec
+    path and behind an element head: at least two whole head workgroups (a
+    wrong block stride shows), at least two whole tail workgroups, a last
+    partial one with a whole wave and a partial wave, and an element tail after
+    the last vector below 16 bytes: on both paths at 1, 2 and 4 bytes; at 8
+    bytes on the vec path only, as no count can do better there (the head
+    path's single head element leaves count - 1 elements, so one of count and
+    count - 1 is a whole number of 2-element vectors).  lanes() itself gives
+    ONE head workgroup here, which is why these forms have a count of their
+    own."""
+    for esz in (1, 2, 4, 8, 16):
+        n = S.fetch_lanes(esz)
+        assert n == (48 * 1024 + 16 * 101) // esz + 1
+        bodies = [(n * esz // 16, n * esz % 16)]
+        if esz < 16:            # head path: (16 - esz) bytes of head elements first
+            bodies.append(((n * esz - (16 - esz)) // 16, (n * esz - (16 - esz)) % 16))
+        for nvec, tail_bytes in bodies:
+            assert 3172 <= nvec <= 3174, (esz, nvec)
+            nhead, whole, part = S.model_taper(nvec, 4)
+            assert nhead >= 2 and whole >= 2, (esz, nvec)
+            assert (nhead, whole) == (2, 4) and 100 <= part <= 102
+            assert part >= 64 and part % 64, (esz, nvec)        # a whole wave, a partial one
+            assert nhead * 1024 + whole * 256 + part == nvec
+            assert tail_bytes % esz == 0
+        tails = [t >= esz for _, t in bodies]
+        assert tails == {8: [True, False], 16: [False]}.get(esz, [True, True]), (esz, bodies)
+        assert S.model_taper(S.lanes(esz) * esz // 16, 4)[0] == 1
+
+
+def test_fetch_form_case_lists():
+    """The fetch and compare form generators: the totals, the form the model
+    names for each as_bytes and functor shape, both paths, the count."""
+    rp, sp = S.rw_pairs(), S.swap_pairs()
+    rng = np.random.default_rng(2)
+    seen, total = set(), 0
+    for op in S.RW_OPS:
+        dts = S.table_dts(rp, op)
+        cases = list(S.readwrite_form_cases(op, dts, rng))
+        assert len(cases) == S.n_fetch_form_cases("readwrite", op, dts)
+        assert len(cases) == (1 if op == S.READ else 2) * S.n_table_cases(dts, S.FORM_PATHS)
+        for form, as_bytes, dt, case in cases:
+            assert S.model_fetch_form(as_bytes, S.fetch_nin("readwrite", op)) == form
+            assert case.path in S.FORM_PATHS
+            assert case.at["dst"][1] == S.fetch_lanes(S.esz_of(dt)) * S.esz_of(dt)
+            assert ("src" in case.at) == (op != S.READ) and "res" in case.at
+            seen.add((form, S.fetch_nin("readwrite", op), (op, dt), case.path))
+        total += len(cases)
+    assert total == N_RW_FORM_CASES == S.N_RW_FORM_CASES == 508
+    total = 0
+    for op in S.SWAP_OPS:
+        dts = S.table_dts(sp, op)
+        cases = list(S.swap_form_cases(op, dts, rng))
+        assert len(cases) == S.n_fetch_form_cases("swap", op, dts)
+        for form, as_bytes, dt, case in cases:
+            assert S.model_fetch_form(as_bytes, 3) == form == "fetch_lds_taper nt"
+            assert case.path in S.FORM_PATHS and set(case.at) == {"dst", "src", "cmp", "res"}
+            assert case.at["dst"][1] == S.fetch_lanes(S.esz_of(dt)) * S.esz_of(dt)
+            seen.add((form, 3, (op, dt), case.path))
+        total += len(cases)
+    assert total == N_SWAP_FORM_CASES == S.N_SWAP_FORM_CASES == 154
+    # every pair under nt on the vec path; every two-input pair under sc1 too
+    for form, nin, pairs in (("fetch_lds_taper nt", None, rp + sp),
+                             ("fetch_lds_taper sc1", 2, [p for p in rp if p[0] != S.READ])):
+        got = {p for f, k, p, path in seen if f == form and path == "vec"}
+        assert got == set(pairs), form
+        head = {p for f, k, p, path in seen if f == form and path == "head"}
+        assert head == {p for p in pairs if S.esz_of(p[1]) < 16}, form
+    assert {(f, k) for f, k, *_ in seen} == {("fetch_lds_taper nt", 1), ("fetch_lds_taper nt", 2),
+                                             ("fetch_lds_taper nt", 3), ("fetch_lds_taper sc1", 2)}
+
+
+@pytest.mark.parametrize("op", S.RW_OPS)
+def test_host_readwrite_form_cases(op):
+    """The fetch form cases through lfa_host_readwrite, which has no forms:
+    this pins fetch_lanes, the layouts and the references before a kernel
+    sees them."""
+    dts = S.table_dts(S.rw_pairs(), op)
+    ran = 0
+    for _, _, dt, case in S.readwrite_form_cases(op, dts, np.random.default_rng(18000 + op)):
+        a = case.arena.copy()
+        atomic.host_readwrite(op, dt, case.view(a, "dst"),
+                              case.view(a, "src") if "src" in case.at else None,
+                              case.view(a, "res"), S.fetch_lanes(S.esz_of(dt)))
+        case.check(dt, a)
+        ran += 1
+    assert ran == (1 if op == S.READ else 2) * S.n_table_cases(dts, S.FORM_PATHS) and ran
+
+
+@pytest.mark.parametrize("op", S.SWAP_OPS)
+def test_host_swap_form_cases(op):
+    dts = S.table_dts(S.swap_pairs(), op)
+    ran = 0
+    for _, _, dt, case in S.swap_form_cases(op, dts, np.random.default_rng(19000 + op)):
+        a = case.arena.copy()
+        atomic.host_swap(op, dt, case.view(a, "dst"), case.view(a, "src"),
+                         case.view(a, "cmp"), case.view(a, "res"), S.fetch_lanes(S.esz_of(dt)))
+        case.check(dt, a)
+        ran += 1
+    assert ran == S.n_table_cases(dts, S.FORM_PATHS) and ran
 
 
 # ------------------------------------------------------------- one-shot ----

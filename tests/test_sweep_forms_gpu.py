@@ -1,5 +1,5 @@
-"""Oracle sweep of the forms the write and tree launchers only take at large
-sizes, run at the sweep's own ~40 KiB shape.
+"""Oracle sweep of the forms the write, tree and fetch launchers only take at
+large sizes, run at the sweep's own ~40 KiB shape (~50 KiB for the fetch forms).
 
 tests/test_sweep_gpu.py and tests/test_sweep_tables_gpu.py run every (op,
 datatype) pair, but at one small shape, where each launcher of
@@ -11,17 +11,24 @@ are separate template instantiations for every pair:
   launch_tree_body  reduce_tree_lds<.., 2, 4, 1>     2 inputs, from 192 MiB
                     reduce_tree_chunk<.., NLEAF, 1>  3..8 inputs, from 192 MiB
                     reduce_tree_chunk<.., NLEAF, 2>  9..32 inputs, from 192 MiB
+  launch_fetch      fetch_lds_taper<4, 1, sc1, RwF>  readwrite but ATOMIC_READ,
+                                                     from 64 MiB
+                    fetch_lds_taper<4, 1, nt, RwF>   every readwrite pair, from 192 MiB
+                    fetch_lds_taper<4, 1, nt, SwapF> every compare pair, from 192 MiB
 
-(launch_fetch's tapered forms, from 64 and 192 MiB, are not covered here:
-test_fetch_compare_nt_path and the 80 MiB fetch tests remain their only runs.)
 The few tests at those sizes (test_tree_nt_forms,
-test_nt_store_path_every_op_family, the tapered-tail tests) stay the proof that
+test_nt_store_path_every_op_family, the tapered-tail tests,
+test_fetch_compare_nt_path) stay the proof that
 the real sizes work end to end, for a handful of pairs on windows of the
-buffer.  Here every pair runs every one of these forms: lfa__write_as and
-lfa__tree_as choose the form as if the vector body were `as_bytes` bytes
+buffer.  Here every pair runs every one of these forms: lfa__write_as,
+lfa__tree_as, lfa__readwrite_as and lfa__swap_as choose the form as if the
+vector body were `as_bytes` bytes
 (lfa_split.h) and take the split, the grid and the arguments from the real
 size, so the kernels are the product's own instantiations on tests/_sweep.py's
-arenas.  Every form is correct at any vector count: a tile that runs past it
+arenas.  The fetch cases have a count of their own (fetch_lanes: launch_fetch
+tapers a quarter, and lanes() would leave it one head workgroup) and the
+tables' own check: res byte for byte the old dst, src and cmp unchanged, dst
+exact for the compare table and ATOMIC_READ.  Every form is correct at any vector count: a tile that runs past it
 takes the guarded path, and the tapered grid of a small body has fewer head
 workgroups (tests/test_sweep_cpu.py holds lanes() to two whole head tiles,
 whole and partial tail tiles, and 5 to 10 whole workgroup tiles of the tree
@@ -49,6 +56,10 @@ OPS = range(10)
 # pairs are 16-byte types, which have no head path
 N_WRITE = 2 * (148 + 126)
 N_TREE = 133 * 7 * 3
+# nt: (pairs + pairs below 16 bytes); tapered write-through: the same without
+# ATOMIC_READ's 13 pairs (2 of the 24 sixteen-byte pairs are its)
+N_RW = (145 + 121) + (132 + 110)
+N_SWAP = 84 + 70
 
 
 @pytest.fixture(scope="module")
@@ -82,6 +93,12 @@ def test_pair_lists_match_the_library(manifest):
     assert len(wp) == 148 and len(S.reduce_pairs()) == 133
     assert sum(2 * _n_cases(S.table_dts(wp, op)) for op in S.WRITE_OPS) == N_WRITE == 548
     assert sum(S.n_tree_form_cases(op) for op in OPS) == N_TREE == 2793
+    rp, sp = S.rw_pairs(), S.swap_pairs()
+    assert len(rp) == 145 and len(sp) == 84
+    assert sum(S.n_fetch_form_cases("readwrite", op, S.table_dts(rp, op))
+               for op in S.RW_OPS) == N_RW == 508
+    assert sum(S.n_fetch_form_cases("swap", op, S.table_dts(sp, op))
+               for op in S.SWAP_OPS) == N_SWAP == 154
 
 
 @pytest.mark.parametrize("op", S.WRITE_OPS)
@@ -119,8 +136,50 @@ def test_tree_forms_every_pair(op):
     assert ran == S.n_tree_form_cases(op) == 21 * len(S.dts_of(op)) and ran
 
 
+@pytest.mark.parametrize("op", S.RW_OPS)
+def test_readwrite_forms_every_pair(op):
+    """fetch_lds_taper with nt stores (as 192 MiB) for every type of the op
+    and, for every op but ATOMIC_READ, with write-through stores (as 64 MiB),
+    on the vec and head paths."""
+    dts = S.table_dts(S.rw_pairs(), op)
+    cases = list(S.readwrite_form_cases(op, dts, np.random.default_rng(18000 + op)))
+    for form, as_bytes, dt, case in cases:
+        t = _upload(case.arena)
+        atomic.readwrite_as(op, dt, case.view(t, "dst"),
+                            case.view(t, "src") if "src" in case.at else None,
+                            case.view(t, "res"), S.fetch_lanes(S.esz_of(dt)), as_bytes)
+        case.what = f"{case.what} as {form}"
+        case.check(dt, t.cpu().numpy())
+    assert len(cases) == S.n_fetch_form_cases("readwrite", op, dts) and dts
+    # 2 forms x (types on the vec path + on the head path, which the row's two
+    # 16-byte types do not have); ATOMIC_READ, 13 types, has one form
+    assert len(cases) == 24 if op == S.READ else len(cases) == {13: 48, 12: 44, 10: 36}[len(dts)]
+    assert {f for f, *_ in cases} == {"fetch_lds_taper nt"} | \
+        (set() if op == S.READ else {"fetch_lds_taper sc1"})
+    assert {c.path for *_, c in cases} == set(S.FORM_PATHS)
+
+
+@pytest.mark.parametrize("op", S.SWAP_OPS)
+def test_swap_forms_every_pair(op):
+    """fetch_lds_taper with nt stores (as 192 MiB) over the three-input
+    compare functor for every type of the op, on the vec and head paths."""
+    dts = S.table_dts(S.swap_pairs(), op)
+    cases = list(S.swap_form_cases(op, dts, np.random.default_rng(19000 + op)))
+    for form, as_bytes, dt, case in cases:
+        t = _upload(case.arena)
+        atomic.swap_as(op, dt, case.view(t, "dst"), case.view(t, "src"), case.view(t, "cmp"),
+                       case.view(t, "res"), S.fetch_lanes(S.esz_of(dt)), as_bytes)
+        case.what = f"{case.what} as {form}"
+        case.check(dt, t.cpu().numpy())
+    assert len(cases) == S.n_fetch_form_cases("swap", op, dts) == _n_cases(dts) and dts
+    assert len(cases) == {13: 24, 12: 22, 10: 18}[len(dts)]
+    assert {f for f, *_ in cases} == {"fetch_lds_taper nt"}
+    assert {c.path for *_, c in cases} == set(S.FORM_PATHS)
+
+
 def test_entries_at_as_zero_and_their_validation(manifest):
-    """lfa__write_as and lfa__tree_as with as_bytes = 0 give a correct result
+    """lfa__write_as, lfa__tree_as, lfa__readwrite_as and lfa__swap_as with
+    as_bytes = 0 give a correct result
     (one pair each, the same check), and refuse what the public calls refuse.
     Which instantiation ran is not visible from here."""
     rng = np.random.default_rng(5)
@@ -140,3 +199,29 @@ def test_entries_at_as_zero_and_their_validation(manifest):
     with pytest.raises(atomic.LfaError) as e:
         atomic.reduce_tree_as(S.SUM, 8, t, [], 1, 0)
     assert e.value.rc == -atomic.LFA_EINVAL
+    # the fetch and compare entries: one pair of each table at as_bytes = 0
+    (_, _, dt, case), *_ = S.readwrite_form_cases(S.SUM, [8], rng)
+    t = _upload(case.arena)
+    atomic.readwrite_as(S.SUM, dt, case.view(t, "dst"), case.view(t, "src"), case.view(t, "res"),
+                        S.fetch_lanes(4), 0)
+    case.check(dt, t.cpu().numpy())
+    (_, _, dt, case), *_ = S.swap_form_cases(S.CSWAP_LE, [8], rng)
+    t = _upload(case.arena)
+    atomic.swap_as(S.CSWAP_LE, dt, case.view(t, "dst"), case.view(t, "src"), case.view(t, "cmp"),
+                   case.view(t, "res"), S.fetch_lanes(4), 0)
+    case.check(dt, t.cpu().numpy())
+    # an op outside the table, then a null res, at as_bytes 0 and forced
+    for as_bytes in (0, 192 * S.MIB):
+        with pytest.raises(atomic.LfaError) as e:
+            atomic.readwrite_as(S.CSWAP, 8, t, t, t, 1, as_bytes)
+        assert e.value.rc == -atomic.LFA_EOPNOTSUPP
+        with pytest.raises(atomic.LfaError) as e:
+            atomic.swap_as(S.SUM, 8, t, t, t, t, 1, as_bytes)
+        assert e.value.rc == -atomic.LFA_EOPNOTSUPP
+        with pytest.raises(atomic.LfaError) as e:
+            atomic.readwrite_as(S.SUM, 8, t, t, None, 1, as_bytes)
+        assert e.value.rc == -atomic.LFA_EINVAL
+        with pytest.raises(atomic.LfaError) as e:
+            atomic.swap_as(S.CSWAP, 8, t, t, t, None, 1, as_bytes)
+        assert e.value.rc == -atomic.LFA_EINVAL
+    assert np.array_equal(t.cpu().numpy()[:64], case.arena[:64])      # the refused calls ran nothing

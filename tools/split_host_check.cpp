@@ -1,8 +1,8 @@
 // split_host_check.cpp — lfa_split.h on the host, as g++ sees it: prints the
 // path and the head / nvec / body / tail split of a grid of (element size,
 // dst offset, src offset, count) cases and the taper split around its tile
-// boundaries, and the form launch_write and launch_tree_body pick by size
-// (lfa_form_write, lfa_form_tree) around every threshold, with and without an
+// boundaries, and the form launch_write, launch_tree_body and launch_fetch pick
+// by size (lfa_form_write, lfa_form_tree, lfa_form_fetch) around every threshold, with and without an
 // as_bytes override, one line each, for tests/test_split_cpu.py to compare with
 // the same quantities computed in Python.  Also built with ASan + UBSan:
 //
@@ -64,6 +64,9 @@ int main() {
       const size_t bytes = lfa_form_bytes(real / 16, as);
       for (int mapped = 0; mapped <= 1; mapped++)
         printf("form write %zu %zu %d %d\n", as, real, mapped, (int)lfa_form_write(bytes, mapped));
+      // ATOMIC_READ, the other readwrite ops, the compare table
+      for (int nin = 1; nin <= 3; nin++)
+        printf("form fetch %zu %zu %d %d\n", as, real, nin, (int)lfa_form_fetch(bytes, nin));
       for (int nsrc = 2; nsrc <= 32; nsrc++) {
         int nleaf = 1;
         while (nleaf * 2 <= nsrc) nleaf *= 2;
